@@ -5,7 +5,7 @@ enumerate -> encode (2-bit keys) -> stable MSD radix sort -> unique k-mers + mul
 `value` is measured at the DEVICE boundary (the bench contract: inputs resident in HBM when the
 timed region starts); the step ends with the whole product resident in HBM -- sorted start
 indices, sorted keys, and per distinct k-mer its first sorted index and multiplicity.  The
-end-to-end boundary of BASELINE.md section 3 is reported beside it: `value_e2e` is one wall-clock
+end-to-end boundary of BASELINE.md section 3 is reported beside it (--full): `value_e2e` is one wall-clock
 interval from the sba in pinned host memory to the product in HBM (gk_set_sequence's transfer --
 2-bit packed chunks and raw DMA chunks -- then one step), and the D2H of the sorted start indices
 is reported apart.
@@ -20,7 +20,11 @@ contiguous range of top key digits (genome_kmers.distributed):
   --exchange a2a: each rank encodes its position share and the k-mers go to their owners in ONE
       all-to-all over RCCL (12 B per k-mer), then each rank sorts what it received.
 
-Also reported: the dominant kernel's roofline (HIP events on the engine's stream) and the CPU
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and the
+dominant kernel's roofline (HIP events on the engine's stream inside the timed steps -- no run of
+its own).  `--dump-outputs DIR` also writes what the last timed step left in HBM (sampled windows,
+DIR/<name>.npy).  `--full` adds everything that takes runs of its own after the timed steps: the
+sorted-order self-check, the transfers and the end-to-end interval (`value_e2e`), and the CPU
 baseline -- the reference algorithm (numba-quicksort restatement, oracle/) on a bounded sample.
 """
 
@@ -61,12 +65,18 @@ def parse():
     ap.add_argument("--genome-len", type=int, default=None, help="c3 genome length (default 3.1e9)")
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sorted-order self-check, the transfers either side of "
+                         "the device boundary, the end-to-end interval and the CPU baseline (a plain run skips them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left in HBM to DIR/<name>.npy (float64; "
+                         "fixed seeded windows of the sorted starts, keys and unique k-mers; one GPU, not --sharded)")
     ap.add_argument("--cpu-sample", type=int, default=4_000_000,
                     help="k-mers in the CPU-baseline sample (starts spread over the whole genome: ~15 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-boundary", action="store_true",
-                    help="skip the transfers either side of the device boundary and the end-to-end interval "
-                         "(profiler counter passes and A/B runs only)")
+                    help="--full without the transfers either side of the device boundary and the end-to-end "
+                         "interval (profiler counter passes and A/B runs only)")
     ap.add_argument("--e2e-reps", type=int, default=5, help="end-to-end intervals per source (median reported)")
     ap.add_argument("--sharded", action="store_true",
                     help="use the multi-GPU path even at N = 1 (exercises it on one GPU)")
@@ -192,6 +202,98 @@ def window_check(eng, sba: np.ndarray, k: int, canonical: bool, width: int = 204
             raise SystemExit(f"bench self-check: sorted order broken at index {off + int(np.argmin(ok))}")
         checked += len(w)
     return checked
+
+
+DUMP_WINDOWS, DUMP_WIDTH, DUMP_SEED = 64, 8192, 20_240_607
+
+
+def _device_read(ptr: int, count: int, dtype) -> np.ndarray:
+    """`count` items of `dtype` at device address `ptr`, copied to the host (hipMemcpy D2H through the
+    HIP runtime that torch and libgkm share, genome_kmers._native._share_hip_runtime)."""
+    import ctypes
+    import importlib.util
+
+    out = np.empty(count, dtype=dtype)
+    if count == 0:
+        return out
+    for root in importlib.util.find_spec("torch").submodule_search_locations:
+        p = Path(root) / "lib" / "libamdhip64.so"
+        if p.exists():
+            hip = ctypes.CDLL(str(p))
+            break
+    else:
+        raise SystemExit("--dump-outputs: torch's libamdhip64.so not found")
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    hip.hipMemcpy.restype = ctypes.c_int
+    rc = hip.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2)
+    if rc != 0:
+        raise SystemExit(f"--dump-outputs: hipMemcpy failed ({rc})")
+    return out
+
+
+def _dump_windows(n: int):
+    """Sorted indices of the dumped sample of an n-long array: everything when it is small, else
+    DUMP_WINDOWS windows of DUMP_WIDTH consecutive items -- both ends and seeded offsets between
+    them (the same for every run with the same n).  Returns [(offset, count)]."""
+    if n <= DUMP_WINDOWS * DUMP_WIDTH:
+        return [(0, n)] if n else []
+    rng = np.random.default_rng(DUMP_SEED)
+    offs = {0, n - DUMP_WIDTH} | {int(o) for o in rng.integers(0, n - DUMP_WIDTH, DUMP_WINDOWS - 2)}
+    return [(o, DUMP_WIDTH) for o in sorted(offs)]
+
+
+def dump_outputs(eng, out_dir: str, log, keys: bool = True, unique: bool = True) -> dict:
+    """What the last step left in HBM -- the arrays a caller of the timed path receives -- as
+    out_dir/<name>.npy in float64 (every value is below 2^53, so exact): `sorted_starts` (the sba start
+    index of every k-mer in sorted order), `sorted_keys_w<i>_hi` / `_lo` (the two 32-bit halves of key
+    word i of every sorted k-mer), `unique_first_index` / `unique_count` (per distinct k-mer its first
+    sorted index and multiplicity) and `counts` ([k-mers, distinct k-mers]).  The full arrays are
+    tens of GB at C3, so fixed windows of them are written (`sample_index`, `unique_sample_index`: the
+    indices the rows come from); below 64 MB in all."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    n = eng.n
+    wins = _dump_windows(n)
+    if keys:
+        starts_ptr, keys_ptr, n_dev, words = eng.device_views()
+    else:
+        (starts_ptr, n_dev), keys_ptr, words = eng.device_starts(), 0, 0
+    if n_dev != n:
+        raise SystemExit(f"--dump-outputs: the device holds {n_dev} k-mers, expected {n}")
+
+    def gather(ptr, width, dtype, windows):
+        if not windows:
+            return np.empty(0, dtype=np.float64)
+        return np.concatenate([_device_read(ptr + width * o, m, dtype) for o, m in windows]).astype(np.float64)
+
+    def index(windows):
+        if not windows:
+            return np.empty(0, dtype=np.float64)
+        return np.concatenate([np.arange(o, o + m, dtype=np.float64) for o, m in windows])
+
+    arrays["sample_index"] = index(wins)
+    arrays["sorted_starts"] = gather(starts_ptr, 4, np.uint32, wins)
+    for w in range(words):  # keys are word-major, stride n
+        kw = np.concatenate([_device_read(keys_ptr + 8 * (w * n + o), m, np.uint64) for o, m in wins]) \
+            if wins else np.empty(0, dtype=np.uint64)
+        arrays[f"sorted_keys_w{w}_hi"] = (kw >> np.uint64(32)).astype(np.float64)
+        arrays[f"sorted_keys_w{w}_lo"] = (kw & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    n_unique = 0
+    if unique:
+        gs_ptr, cnt_ptr, n_unique = eng.device_unique()
+        uwins = _dump_windows(n_unique)
+        arrays["unique_sample_index"] = index(uwins)
+        arrays["unique_first_index"] = gather(gs_ptr, 4, np.uint32, uwins)
+        arrays["unique_count"] = gather(cnt_ptr, 4, np.uint32, uwins)
+    arrays["counts"] = np.array([n, n_unique], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB budget")
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out}")
+    return {"dir": str(out), "arrays": sorted(arrays), "bytes": total}
 
 
 def transfer_times(torch, eng, sba, seg, log, reps: int = 3) -> dict:
@@ -387,14 +489,10 @@ def run_ref_profile(args, torch, result_out, log):
     dt = time.perf_counter() - t0
     report = eng.profile_report()
     eng.profile_enable(False)
-    checked = order_check(eng, sba, M)
+    dumped = dump_outputs(eng, args.dump_outputs, log, keys=False, unique=False) if args.dump_outputs else None
+    checked = order_check(eng, sba, M) if args.full else None
     words, bits, _ = eng.key_layout()
     stages = {name: round(v["total_ms"] / args.steps, 3) for name, v in report.items()}
-    # the whole step against the HBM peak: the algorithmic bytes of every priced stage per step over
-    # the step's wall time (the dominant kernel's `frac` is one kernel; this is all of them, and the
-    # step's unpriced remainder -- scans, classify, host round trips -- counts as time)
-    step_bytes = sum(stage_bytes(n, v) for n, v in report.items() if v.get("total_ms", 0) > 0) / args.steps
-    step_frac = step_bytes / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * 1e9)
     msd = "radix_pass" not in report and any(k.startswith("msd_") for k in report)
     if not msd:
         # dominant kernel: the LSD onesweep pass (every radix_pass launch: keys W words + start in and out)
@@ -428,7 +526,7 @@ def run_ref_profile(args, torch, result_out, log):
     units = rp["units"] / max(rp["count"], 1)
     achieved = per_unit * units / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # DRAM regime: 2M starts spread over the whole sba (every position outside '$' is a start)
         valid = np.flatnonzero(sba != 36).astype(np.uint32)
         sample = valid[:: max(1, len(valid) // 2_000_000)]
@@ -456,7 +554,10 @@ def run_ref_profile(args, torch, result_out, log):
                 "gk_reference_random_bases)",
         "boundary": "device: sba resident in HBM; step = enumerate + sort (the call the reference times); sorted "
                     "starts and keys (M=20) / ranks (M=None) resident at the end",
-        "self_check": f"{checked:,} sorted k-mers in windows re-checked against the sba bytes",
+        "full": args.full,
+        "self_check": (f"{checked:,} sorted k-mers in windows re-checked against the sba bytes"
+                       if checked is not None else None),
+        **({} if dumped is None else {"dumped_outputs": dumped}),
         "config": {"workload": f"ref_profile: {args.ref_bases:,} bases in 10 contigs, min_kmer_len=1, "
                                f"max_kmer_len={M}", "kmers": n,
                    "sort_path": (("MSD levels over" if msd else "LSD onesweep over") + " (2-bit padded, length) keys")
@@ -487,6 +588,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    if args.dump_outputs and (world > 1 or args.sharded):
+        raise SystemExit("--dump-outputs writes the single-GPU product (--gpus 1, not --sharded)")
     torch.cuda.set_device(local)
     dist = None
     if world > 1 or args.sharded:
@@ -585,22 +688,26 @@ def main():
 
     ms_per_step = dt / args.steps * 1e3
     value = n_units * args.steps / dt
+    dumped = dump_outputs(eng, args.dump_outputs, log) if args.dump_outputs else None
 
-    # the product's boundary: self-check, then the transfers either side of the device boundary
+    # --full, the product's boundary: self-check, then the transfers either side of the device boundary
     # (timing experiments of a stage's memory floor write wrong output on purpose: no check)
-    checked = (0 if os.environ.get("GKM_EXP_WAVECOPY") or os.environ.get("GKM_EXP_L0")
-               else window_check(eng, sba, k, canonical))
-    if dist is not None:
-        t = torch.tensor([job.local_kmers], dtype=torch.int64, device="cuda")
-        dist.all_reduce(t)
-        if int(t.item()) != n_units:
-            raise SystemExit(f"bench self-check: ranks hold {int(t.item())} k-mers, expected {n_units}")
+    checked = None
+    if args.full:
+        checked = (0 if os.environ.get("GKM_EXP_WAVECOPY") or os.environ.get("GKM_EXP_L0")
+                   else window_check(eng, sba, k, canonical))
+        if dist is not None:
+            t = torch.tensor([job.local_kmers], dtype=torch.int64, device="cuda")
+            dist.all_reduce(t)
+            if int(t.item()) != n_units:
+                raise SystemExit(f"bench self-check: ranks hold {int(t.item())} k-mers, expected {n_units}")
     e2e, e2e_ms = None, None
-    if args.no_boundary:
+    no_boundary = args.no_boundary or not args.full
+    if no_boundary:
         boundary = {"set_sequence_ms": None, "d2h_starts_ms": None}
     else:
         boundary = transfer_times(torch, eng, sba, seg, log)
-    if args.no_boundary:
+    if no_boundary:
         pass
     elif dist is None:
         # the sort hint applies to the fixed-length forward sort of an ACGT sequence (C3; any number of
@@ -736,7 +843,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(sba, k, args.cpu_sample, n_units)
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "k-mers/s", "n_gpus": world, "steps": args.steps,
@@ -759,7 +866,10 @@ def main():
             "value_e2e": round(value_e2e, 1) if value_e2e else None, "e2e_ms": round(e2e_ms, 2) if e2e_ms else None,
             **({} if e2e is None else {"e2e": e2e}),
             "set_sequence_ms": boundary["set_sequence_ms"], "d2h_starts_ms": boundary["d2h_starts_ms"],
-            "self_check": f"{checked:,} sorted k-mers in windows re-checked against the sba bytes",
+            "full": args.full,
+            "self_check": (f"{checked:,} sorted k-mers in windows re-checked against the sba bytes"
+                           if checked is not None else None),
+            **({} if dumped is None else {"dumped_outputs": dumped}),
             "config": {"workload": workload,
                        "genome_bases": L, "k": k, "kmers": n_units, "unique_kmers": n_unique,
                        "parallelism": ("1 GPU" if dist is None else

@@ -38,14 +38,14 @@ for task in "$@"; do
       tail -1 gpurun_out/smoke.log ;;
     bench)
       cfg=${arg%%:*}; tag=${arg#*:}; [ "$tag" = "$arg" ] && tag=$cfg
-      timeout -k 10 600 python -u bench.py --config "$cfg" --steps "$STEPS" --warmup "$WARM" ${BENCH_ARGS:-} \
+      timeout -k 10 600 python -u bench.py --full --config "$cfg" --steps "$STEPS" --warmup "$WARM" ${BENCH_ARGS:-} \
         > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err || { tail -20 gpurun_out/bench_$tag.err; die bench; }
       python3 tools/line_brief.py gpurun_out/bench_$tag.json ;;
     prof)
       cfg=${arg%%:*}; tag=${arg#*:}; [ "$tag" = "$arg" ] && tag=$cfg
       O=gpurun_out/prof_$tag
       mkdir -p $O
-      B=(bench.py --config "$cfg" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline)
+      B=(bench.py --full --config "$cfg" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline)
       smi $O/smi_before.txt
       timeout -k 10 600 python -u "${B[@]}" > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err \
         || { tail -20 $O/bench_unprofiled.err; die prof-bench; }

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 cd $R
-timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 > $OUT/bench.log 2>&1
+timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 2 > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 cd $R
