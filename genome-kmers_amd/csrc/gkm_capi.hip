@@ -12,6 +12,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 
 #include "gkm_internal.h"
 #include "gkm_partition.h"
@@ -22,24 +23,50 @@ namespace gkm {
 // options (gk_set_option): test and tuning overrides of the GKM_* knobs, process-wide
 // ---------------------------------------------------------------------------------------------
 namespace {
+// every knob the library reads through opt(); gk_set_option refuses any other name.  env: the
+// operational knobs the environment may also set (transfer, packer, rank fallback, prefetch,
+// tracing, mapped buffers); everything else needs gk_set_option.  (GKM_FASTA_CHUNK is not here: the
+// FASTA reader, plain C++ beside the library, reads it from the environment itself.)
+struct Knob {
+    const char *name;
+    bool env;
+};
+constexpr Knob kKnobs[] = {
+    // operational
+    {"GKM_RANK_BALLOT", true},      {"GKM_PACK_IMPL", true},        {"GKM_PACK_MIN", true},
+    {"GKM_PACK_BLOCKS", true},      {"GKM_XFER_THREADS", true},     {"GKM_XFER_HYBRID", true},
+    {"GKM_XFER_NUMA", true},        {"GKM_NO_RESIDENT_PACK", true}, {"GKM_PREFETCH_REGIONS", true},
+    {"GKM_MSD_TRACE", true},        {"GKM_VMM_CHUNK_MB", true},
+    // alternative sort paths that the tests or the benchmark compare
+    {"GKM_WIDE_L0", false},         {"GKM_OWN_L0_COMPACT", false},  {"GKM_RANGE_FUSED", false},
+    {"GKM_NO_COMPACT", false},      {"GKM_LEVEL_BITS", false},      {"GKM_NO_FUSED_UNIFORM", false},
+    {"GKM_NO_MERGE_KEYS", false},   {"GKM_SORT_KEYS_LSD", false},   {"GKM_MSD_KEYS_MIN", false},
+    // tests: forced formats and chunk sizes
+    {"GKM_TEST_PAIRS", false},      {"GKM_TEST_P88", false},        {"GKM_TEST_CHUNK_TILES", false},
+    {"GKM_TEST_SCAN_CHUNK", false}, {"GKM_TEST_SEG_SCAN_MULTI", false}, {"GKM_TEST_CHECK_TILES", false},
+    {"GKM_TEST_VMM_MIN_KB", false},
+};
+const Knob *find_knob(const char *name) {
+    for (const Knob &k : kKnobs)
+        if (std::strcmp(k.name, name) == 0) return &k;
+    return nullptr;
+}
+
 std::mutex g_opt_mu;
-std::map<std::string, std::string> g_opts;
-// the operational knobs the environment may still set (transfer, packer, rank fallback, prefetch,
-// tracing); everything else needs gk_set_option
-const char *const kEnvKnobs[] = {"GKM_RANK_BALLOT", "GKM_PACK_IMPL",       "GKM_PACK_MIN",        "GKM_PACK_BLOCKS",
-                                 "GKM_XFER_THREADS", "GKM_XFER_HYBRID",    "GKM_XFER_NUMA",       "GKM_NO_RESIDENT_PACK",
-                                 "GKM_PREFETCH_REGIONS", "GKM_MSD_TRACE",   "GKM_VMM_CHUNK_MB"};
+// the overrides point into g_opt_values, which only grows: a pointer opt() returned stays valid
+// whatever gk_set_option does later (the set of values a process ever sets is tiny)
+std::set<std::string> g_opt_values;
+std::map<std::string, const char *> g_opts;
 }  // namespace
 
 const char *opt(const char *name) {
     {
         std::lock_guard<std::mutex> lk(g_opt_mu);
         auto it = g_opts.find(name);
-        if (it != g_opts.end()) return it->second.c_str();  // (stable until the option is set again)
+        if (it != g_opts.end()) return it->second;
     }
-    for (const char *e : kEnvKnobs)
-        if (std::strcmp(e, name) == 0) return std::getenv(name);
-    return nullptr;
+    const Knob *k = find_knob(name);
+    return k && k->env ? std::getenv(name) : nullptr;
 }
 
 // Large device buffers (the k-mer arrays, the sort's scratch): hipMalloc, or -- GKM_VMM_CHUNK_MB=N,
@@ -642,11 +669,6 @@ extern "C" int gk_set_sequence(gk_ctx *c, const uint8_t *sba, uint64_t len, cons
         // device (gkm_xfer.hip); the stream orders the sort's kernels behind the last unpack, so
         // only the census is waited for
         uint64_t dollars = 0;
-        // (A/B: GKM_EARLY_ELEMS=1 -- the k-mer buffers for every position allocated here, before the
-        // transfer's staging slots, as the prefetch path does)
-        static const bool early = opt("GKM_EARLY_ELEMS") != nullptr;
-        if (early)
-            if (int rc = ensure_elems(c, len, 1)) return rc;
         // a sort hint (gk_sort_hint): the L0 pass of gk_sort(k) runs as the sequence lands
         L0Prefetch *pf = nullptr;
         if (c->hint_k && !internal)
@@ -662,7 +684,6 @@ extern "C" int gk_set_sequence(gk_ctx *c, const uint8_t *sba, uint64_t len, cons
     }
     c->have_starts = c->sorted = c->keys_valid = c->enumerated = c->unique_valid = c->heads_valid = c->canonical = false;
     c->enum_sorted = false;
-    c->pk_fresh = false;
     if (len < packed_transfer_min()) c->res_pk = false;  // (the packed transfer sets it)
     c->n = 0;
     if (h[0] & 4u) return fail(c, GK_E_ALPHABET, "Sequence contains non-allowed characters!");
@@ -701,9 +722,9 @@ extern "C" int gk_resident_packed(gk_ctx *c, int *on) {
 }
 
 extern "C" int gk_set_option(const char *name, const char *value) {
-    if (!name || std::strncmp(name, "GKM_", 4) != 0) return GK_E_ARG;
+    if (!name || !find_knob(name)) return GK_E_ARG;  // (a retired or misspelt knob fails loudly)
     std::lock_guard<std::mutex> lk(g_opt_mu);
-    if (value) g_opts[name] = value;
+    if (value) g_opts[name] = g_opt_values.insert(value).first->c_str();
     else g_opts.erase(name);
     return GK_OK;
 }
@@ -797,12 +818,11 @@ int gkm::ensure_keys(gk_ctx *c) {
     timer_begin(c, "reencode_keys", &slot);
     // multi-word keys of a sorted enumeration: through an enumeration-order table in the free key
     // buffer (one aligned row per k-mer instead of a ~70-byte window at a random position)
-    static const bool no_table = opt("GKM_NO_KEY_TABLE") != nullptr;  // (A/B)
     const KeySpec &ks = c->spec;
     // (the table path answers hipErrorNotSupported when it does not apply -- e.g. per-contig k-mer
     // counts that do not add up to n -- and the window gather, always correct, runs instead)
     hipError_t te = hipErrorNotSupported;
-    if (c->enum_sorted && !no_table && ks.words >= 2 && ks.symbols == ks.min_len && ks.symbols <= 64 &&
+    if (c->enum_sorted && ks.words >= 2 && ks.symbols == ks.min_len && ks.symbols <= 64 &&
         (ks.bits == 2 || ks.bits == 4) && c->n >= 4096 && c->key_words_b[c->cur ^ 1] >= ks.words)
         te = launch_encode_table_gather(c, ks, c->vals[c->cur], c->n, c->keys[c->cur], c->keys[c->cur ^ 1],
                                         8 * (uint64_t)c->key_words_b[c->cur ^ 1] * (c->elem_cap + 64));
@@ -818,16 +838,13 @@ int gkm::ensure_keys(gk_ctx *c) {
 
 static int sort_direct(gk_ctx *c, const KeySpec &ks) {
     // fixed-length keys (k <= 64) from the enumerated starts: stable MSD in one-word phases (gkm_msd.hip)
-    static const bool force_lsd = opt("GKM_SORT_LSD") != nullptr;
-    const bool msd =
-        c->enumerated && ks.symbols == ks.min_len && ks.symbols <= 64 && (ks.bits == 2 || ks.bits == 4) && !force_lsd;
+    const bool msd = c->enumerated && ks.symbols == ks.min_len && ks.symbols <= 64 && (ks.bits == 2 || ks.bits == 4);
     int rc = ensure_elems(c, c->n, msd ? 1 : ks.words);
     if (rc != GK_OK) return rc;
     if (msd) {
         // a mixed sba (N runs, IUPAC letters): ACGT-only k-mers on 2-bit keys, the rest apart
-        static const bool no_split = opt("GKM_NO_SPLIT") != nullptr;
         bool split = false;
-        if (!c->acgt && !no_split) {
+        if (!c->acgt) {
             rc = split_sort(c, ks, &split);
             if (rc != GK_OK) return rc;
         }
@@ -897,12 +914,11 @@ static int sort_doubling(gk_ctx *c, uint32_t M) {
 
     // seed keys: ACGT data as 29 symbols of 2 bits + a 5-bit length field (the (padded, length)
     // keys of the bounded sort: the same order as '$'-terminated 3-bit codes, 29 symbols instead of
-    // 21, and every key bit carries information for the MSD levels; GKM_SEED3=1 keeps the 3-bit
-    // seeds); other data as 16 symbols of 4 bits
-    static const bool seed3 = opt("GKM_SEED3") != nullptr;
+    // 21, and every key bit carries information for the MSD levels); other data as 16 symbols of
+    // 4 bits
     KeySpec seed{};
-    seed.bits = c->acgt ? (seed3 ? 3 : 2) : 4;
-    seed.symbols = c->acgt ? (seed3 ? 21 : 29) : 16;
+    seed.bits = c->acgt ? 2 : 4;
+    seed.symbols = c->acgt ? 29 : 16;
     seed.lenbits = seed.bits == 2 ? bit_width((uint64_t)seed.symbols) : 0;
     seed.min_len = 1;
     seed.words = 1;
@@ -912,7 +928,7 @@ static int sort_doubling(gk_ctx *c, uint32_t M) {
     int slot;
     // large universes: the rounds sort only the groups still tied (MSD, msd_sort_groups); small ones
     // re-sort the whole array by rank pairs each round (LSD)
-    const bool by_groups = sort_keys_msd(c, n1, 1, 64) && opt("GKM_DOUBLING_FULL") == nullptr;
+    const bool by_groups = sort_keys_msd(c, n1, 1, 64);
     timer_begin(c, "encode", &slot);
     timer_units(c, slot, n1);
     const bool seed_hist = !sort_keys_msd(c, n1, 1, seed.total_bits);
@@ -1218,12 +1234,11 @@ extern "C" int gk_sort(gk_ctx *c, uint32_t max_kmer_len, uint32_t flags) {
     // keys, then only the groups still tied -- instead of one LSD pass per 8 bits of the 2-word
     // keys (13 passes, 21 ms for the reference's max-50 workload).  The doubling ranks every
     // position of the sequence, so a subset of user-given starts (n well below the positions)
-    // keeps the direct keys (GKM_BOUNDED_DIRECT=1 keeps them always).  The sort's keys are then
+    // keeps the direct keys.  The sort's keys are then
     // ranks; the key contract stays the direct one: they are re-encoded from the sorted starts
     // when asked for (keys_stale)
     const bool reroute = direct && ks.words >= 2 && !canonical && max_kmer_len != c->min_k && c->acgt &&
-                         (from_enum || 2 * c->n >= c->sba_len) && sort_keys_msd(c, c->n, 1, 64) &&
-                         opt("GKM_BOUNDED_DIRECT") == nullptr;
+                         (from_enum || 2 * c->n >= c->sba_len) && sort_keys_msd(c, c->n, 1, 64);
     if (reroute) direct = false;
     rc = direct ? sort_direct(c, ks) : sort_doubling(c, max_kmer_len);
     if (rc != GK_OK) return rc;

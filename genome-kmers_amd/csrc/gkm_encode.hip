@@ -54,7 +54,6 @@ __device__ __forceinline__ uint32_t code2(uint32_t c) { return ((c >> 1) ^ (c >>
 template <int BITS>
 __device__ __forceinline__ uint32_t sym_code(uint32_t c, const uint8_t *lut4) {
     if (BITS == 2) return code2(c);
-    if (BITS == 3) return c == GK_DOLLAR ? 0u : code2(c) + 1u;
     return lut4[c];
 }
 
@@ -319,8 +318,8 @@ __global__ __launch_bounds__(256) void encode_roll_w1_kernel(const uint8_t *__re
 }
 
 // ---------------------------------------------------------------------------------------------
-// bounded variable-length keys of one word (2-bit ACGT with a length field, the 3-bit doubling
-// seeds), rolling: thread t rolls the raw window over positions 16t .. 16t+15 as encode_roll_w1
+// bounded variable-length keys of one word (2-bit ACGT with a length field: bounded sorts,
+// the doubling seeds), rolling: thread t rolls the raw window over positions 16t .. 16t+15 as encode_roll_w1
 // does, and a '$' bitmask of its bytes gives each position's first '$' -- the symbols from it on
 // are zeroed and the length field is min(len, symbols), window_key's encoding (sort_keys' MSD path:
 // no digit histograms).  The per-position byte loop of encode_generic_kernel ran 1.05 ms for 1e8
@@ -976,23 +975,17 @@ hipError_t launch_encode_positions(gk_ctx *c, const KeySpec &ks, uint64_t *keys,
                                c->seg, (uint32_t)c->nseg, k, keys, vals, hist);
         return hipGetLastError();
     }
-    static const bool no_roll = opt("GKM_NO_ROLL_BOUNDED") != nullptr;  // (A/B)
-    static const bool no_roll_hist = opt("GKM_NO_ROLL_HIST") != nullptr;  // (A/B)
-    if (bounded && (hist == nullptr || (!no_roll_hist && k.digits <= 8)) && ks.words == 1 &&
-        (ks.bits == 2 || ks.bits == 3) && ks.symbols <= 32 && ks.min_len >= 1 && !no_roll) {
+    if (bounded && (hist == nullptr || k.digits <= 8) && ks.words == 1 && ks.bits == 2 && ks.symbols <= 32 &&
+        ks.min_len >= 1) {
         auto go = [&](auto fn) {
             hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, c->stream, c->sba, c->sba_len, c->seg, (uint32_t)c->nseg,
                                k, keys, vals, hist);
         };
-        if (ks.bits == 2)
-            hist ? go(encode_roll_bounded_kernel<2, true>) : go(encode_roll_bounded_kernel<2, false>);
-        else
-            hist ? go(encode_roll_bounded_kernel<3, true>) : go(encode_roll_bounded_kernel<3, false>);
+        hist ? go(encode_roll_bounded_kernel<2, true>) : go(encode_roll_bounded_kernel<2, false>);
         return hipGetLastError();
     }
     if (ks.bits == 2) return bounded ? dispatch_generic_w<2, true>(c, k, keys, vals, hist, grid)
                                      : dispatch_generic_w<2, false>(c, k, keys, vals, hist, grid);
-    if (ks.bits == 3) return dispatch_generic_w<3, true>(c, k, keys, vals, hist, grid);
     return bounded ? dispatch_generic_w<4, true>(c, k, keys, vals, hist, grid)
                    : dispatch_generic_w<4, false>(c, k, keys, vals, hist, grid);
 }
@@ -1033,9 +1026,6 @@ hipError_t launch_member_seed_keys(gk_ctx *c, const KeySpec &seed, const uint8_t
     if (seed.bits == 2)
         hipLaunchKernelGGL(member_seed_key_kernel<2>, dim3(grid), dim3(256), 0, c->stream, c->sba, k, flags, vals, c->seg,
                            (uint32_t)c->nseg, (uint64_t)c->sba_len, o, n, keys);
-    else if (seed.bits == 3)
-        hipLaunchKernelGGL(member_seed_key_kernel<3>, dim3(grid), dim3(256), 0, c->stream, c->sba, k, flags, vals, c->seg,
-                           (uint32_t)c->nseg, (uint64_t)c->sba_len, o, n, keys);
     else
         hipLaunchKernelGGL(member_seed_key_kernel<4>, dim3(grid), dim3(256), 0, c->stream, c->sba, k, flags, vals, c->seg,
                            (uint32_t)c->nseg, (uint64_t)c->sba_len, o, n, keys);
@@ -1046,9 +1036,8 @@ template <int W, int BITS, bool BOUNDED>
 static hipError_t gather_w(gk_ctx *c, const KS &k, const uint32_t *starts, uint64_t n, uint64_t *keys) {
     int grid = (int)std::min<uint64_t>((n + 255) / 256, 8192);
     if (grid < 1) grid = 1;
-    static const bool slow = opt("GKM_GATHER_SLOW") != nullptr;  // A/B of the per-byte path
     if constexpr (!BOUNDED && (BITS == 2 || BITS == 4))
-        if (k.symbols <= 64 && !slow) {
+        if (k.symbols <= 64) {
             hipLaunchKernelGGL((encode_gather_fast_kernel<W, BITS>), dim3(grid), dim3(256), 0, c->stream, c->sba, k,
                                starts, n, keys);
             return hipGetLastError();
@@ -1075,10 +1064,9 @@ hipError_t launch_encode_table_gather(gk_ctx *c, const KeySpec &ks, const uint32
     if (e != hipSuccess) return e;
     KS k = pod(ks);
     // the position-indexed 2-bit rows when they fit the table buffer (k <= 63)
-    static const bool enum_rows = opt("GKM_KEY_TABLE_ENUM") != nullptr;  // (A/B: the W-word rows)
     // (the rows, then the fix-up list of marker entries -- at most n -- in the same buffer)
     const uint64_t rows_bytes = 16 * (((uint64_t)c->sba_len + kRowPos - 1) / kRowPos * kRowPos);
-    if (!enum_rows && ks.symbols <= 63 && rows_bytes + 4 * (n + 64) <= table_bytes) {
+    if (ks.symbols <= 63 && rows_bytes + 4 * (n + 64) <= table_bytes) {
         uint32_t *fix_idx = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(table) + rows_bytes);
         uint32_t *fix_cnt = nullptr;
         if (scratch(c, "rows_fix_cnt", 64, &fix_cnt) != hipSuccess) return hipErrorOutOfMemory;
@@ -1127,7 +1115,6 @@ hipError_t launch_encode_gather(gk_ctx *c, const KeySpec &ks, const uint32_t *st
     const bool bounded = ks.symbols != ks.min_len;
     if (ks.bits == 2) return bounded ? gather_dispatch<2, true>(c, k, starts, n, keys)
                                      : gather_dispatch<2, false>(c, k, starts, n, keys);
-    if (ks.bits == 3) return gather_dispatch<3, true>(c, k, starts, n, keys);
     return bounded ? gather_dispatch<4, true>(c, k, starts, n, keys) : gather_dispatch<4, false>(c, k, starts, n, keys);
 }
 

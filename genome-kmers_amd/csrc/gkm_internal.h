@@ -39,7 +39,6 @@ constexpr int kScanTile = kScanThreads * kScanItems;
 
 // How a k-mer is turned into an order-preserving integer key:
 //   bits   2: A,C,G,T -> 0..3 (sba holds only ACGT)
-//          3: '$'/end -> 0, A,C,G,T -> 1..4 (doubling seeds on ACGT data under GKM_SEED3=1)
 //          4: '$'/end -> 0, A B C D G H K M N R S T V W Y -> 1..15 (IUPAC data)
 //   symbols  number of leading symbols encoded (= max_kmer_len for direct keys)
 //   lenbits  2-bit keys of variable length append min(len, symbols) in the low lenbits bits
@@ -82,8 +81,6 @@ struct gk_ctx {
     uint32_t *res_dol = nullptr;
     uint64_t res_code_cap = 0, res_dol_cap = 0;
     bool res_pk = false;
-    bool pk_fresh = false;  // the packed sequence (scratch "pk_code" / "pk_dol") is current for
-                            // the next gk_shard_sort_range (set by gk_shard_histogram)
 
     // k-mers
     uint64_t n = 0;
@@ -197,19 +194,13 @@ struct gk_ctx {
 // ---------------------------------------------------------------------------------------------
 namespace gkm {
 
-// Test and tuning overrides (GKM_* names, gkm_capi.hip): the value gk_set_option gave `name`, else
-// -- for the few operational knobs listed in gkm_capi.hip (transfer threads and chunking, the
-// packer, the rank fallback, prefetch regions, tracing) -- the environment variable; nullptr when
-// unset.  Every other knob (alternative sort paths, test-only chunk sizes and forced formats) is
-// reachable only through gk_set_option, so no user environment can change the sort path silently.
+// Test and tuning overrides (the GKM_* names of kKnobs, gkm_capi.hip): the value gk_set_option gave
+// `name`, else -- for the operational knobs the table marks (transfer threads and chunking, the
+// packer, the rank fallback, prefetch regions, tracing, mapped buffers) -- the environment variable;
+// nullptr when unset.  Every other knob (alternative sort paths, test-only chunk sizes and forced
+// formats) is reachable only through gk_set_option, so no user environment can change the sort path
+// silently.  The pointer stays valid for the life of the process (values are interned).
 const char *opt(const char *name);
-// timing experiments that write wrong output on purpose (GKM_EXP_*, GKM_L0_PROF): only in builds
-// with -DGKM_EXPERIMENTS (tools/build_variant.sh), never in the product library
-#ifdef GKM_EXPERIMENTS
-inline const char *exp_opt(const char *name) { return std::getenv(name); }
-#else
-inline const char *exp_opt(const char *) { return nullptr; }
-#endif
 
 hipError_t ensure(void **p, uint64_t *cap, uint64_t bytes);
 // large device buffers (gkm_capi.hip): hipMalloc, or an address range mapped from physical

@@ -106,9 +106,11 @@ struct L0Args {
     // 2-bit packed copy of an ACGT sba (pack2_kernel, 32 positions per word; null: pack bytes)
     const uint64_t *pk_code = nullptr;
     const uint32_t *pk_dol = nullptr;
-    // timing builds only (GKM_L0_PROF): per-phase clock sums of the L0 partition's first and last
-    // wave of every workgroup
-    unsigned long long *prof = nullptr;
+    // unused: holds the place of a removed profiling pointer.  Every L0 kernel takes this struct by
+    // value, and dropping the 8 bytes moves the kernel arguments behind it, which changed the
+    // register allocation of the tuned kernels (other SGPR spill counts in msd0_pipe_kernel); to be
+    // removed together with an A/B run of the L0 passes
+    uint64_t reserved = 0;
 };
 
 __device__ __forceinline__ bool l0_owned(uint32_t d, const L0Args &a) { return d - a.own_lo < a.own_span; }
@@ -405,11 +407,8 @@ __global__ __launch_bounds__(T) void msd0_count_kernel(L0Args a, Dig d0, uint32_
 // are double-buffered (2 x (48 + 6) KB at 24,576 positions), so the previous tile's stores are
 // spread over EVERY phase of this tile -- packing, ranking, scan, staging -- and the memory pipe
 // never idles (staged as (key, start) in one 135 KB buffer, the stores had to finish before the
-// staging: a phase profile (GKM_L0_PROF) showed them issued in 45 % of the tile time, backed up,
-// and the pipe idle for the rest).  Twice the tile of the level passes: runs of ~192 per digit.
-// PROF (timing builds, GKM_L0_PROF): the first and the last wave of each workgroup add the clock
-// ticks of every phase of the tile loop to a.prof[wave != 0][phase]
-constexpr int kL0Phases = 9;
+// staging: a phase profile showed them issued in 45 % of the tile time, backed up, and the pipe
+// idle for the rest).  Twice the tile of the level passes: runs of ~192 per digit.
 #ifndef GKM_L0_T
 #define GKM_L0_T 1024
 #endif
@@ -427,8 +426,7 @@ constexpr int kP0Tile = kP0T * kP0I;     // 24,576 (< 65,536: positions staged a
 // OWN (the key-range ranks' fused select, round 5): only k-mers whose ownership digit (the top
 // a.own_bits key bits) is in the rank's range are partitioned -- the select pass and its 13-byte
 // round trip per kept k-mer fall away
-template <int BITS, int T, int I, int R, bool ND, bool CANON = false, bool PROF = false, bool P88 = false,
-          bool OWN = false>
+template <int BITS, int T, int I, int R, bool ND, bool CANON = false, bool P88 = false, bool OWN = false>
 __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const uint32_t *__restrict__ tile_off,
                                                       uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
                                                       uint32_t ntiles, uint64_t sink, NextDigits nd) {
@@ -497,17 +495,6 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
     };
     if (walk.first < walk.end) load(walk.first);
     __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    const bool pw = PROF && lane == 0 && (wave == 0 || wave == NW - 1);
-    unsigned long long ph[kL0Phases] = {0}, tp = PROF ? clock64() : 0;
-    auto mark = [&](int k) {
-        if constexpr (PROF) {
-            if (pw) {
-                const unsigned long long t1 = clock64();
-                ph[k] += t1 - tp;
-                tp = t1;
-            }
-        }
-    };
     for (uint32_t t = walk.first; t < walk.end; t += walk.step) {
         uint32_t *wc = s_wc + wave * RADIX;
 #pragma unroll
@@ -518,12 +505,9 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
         // rr and toff are consumed: the next tile's bytes fly during this whole tile (the last
         // tile re-loads itself, so every iteration issues the same loads: static wait counts)
         load(min(t + walk.step, walk.end - 1));
-        mark(0);
 #pragma unroll
         for (int g = 0; g < G_TOP; ++g) store_group(g);
-        mark(1);
         lds_barrier();  // packed codes visible
-        mark(2);
         const uint64_t P0 = a.lo + (uint64_t)t * TILE;
         // a tile without stops that ends before a.hi: every position starts a k-mer (wave-uniform)
         uint32_t anystop = 0;
@@ -534,7 +518,6 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
         uint32_t dr[I], validm = 0;  // per item: digit | rank << 8 (rank < I * 64)
         uint32_t p0 = wave * (I * 64) + lane;
         asm volatile("" : "+v"(p0));
-        mark(3);
 #pragma unroll
         for (int i = 0; i < I; ++i) {
             const uint32_t p = p0 + i * 64;
@@ -549,9 +532,7 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
             if (i < G_RANK) store_group(G_TOP + i);
             __builtin_amdgcn_sched_barrier(0);  // one item at a time (register pressure, see above)
         }
-        mark(4);
         lds_barrier();  // ranks final
-        mark(5);
         uint32_t total = 0, incl = 0;
         if (tid < RADIX) {
 #pragma unroll
@@ -575,7 +556,6 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
             if (tid == RADIX - 1) s_start[RADIX] = pre + incl;
         }
         lds_barrier();
-        mark(6);
 #pragma unroll
         for (int i = 0; i < I; ++i) {
             const bool valid = (validm >> i) & 1u;
@@ -586,83 +566,18 @@ __global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const ui
         const uint32_t cnt = s_start[RADIX];
 #pragma unroll
         for (int g = G_TOP + G_RANK + G_SCAN; g < I; ++g) store_group(g);
-        mark(7);
         pcnt = cnt;
         pP0 = P0;
         lds_barrier();  // staging complete; counters, codes and the previous staging read
-        mark(8);
         b ^= 1;
     }
     if (walk.first < walk.end) {
 #pragma unroll
         for (int g = 0; g < I; ++g) store_group(g);
     }
-    if constexpr (PROF) {
-        if (pw)
-            for (int k = 0; k < kL0Phases; ++k) atomicAdd(&a.prof[(wave != 0) * kL0Phases + k], ph[k]);
-    }
 }
 
-// TIMING EXPERIMENTS ONLY (GKM_EXP_L0=1, wrong output): the L0 partition's memory traffic with no
-// encoding or ranking -- each persistent workgroup walks the same tiles (XCD-aware), reads the
-// tile's sequence bytes, and writes (key, start, digit byte) for every position to 2^R runs of
-// TILE / 2^R consecutive slots per tile, run d of tile t at d * (n / 2^R) + t * (TILE / 2^R): the
-// real layout of an L0 output over uniform digits.  Its time is the floor of the L0's scatter.
-template <int T, int I, int R>
-__global__ __launch_bounds__(T) void l0_scatter_floor_kernel(const uint8_t *__restrict__ sba, uint64_t n,
-                                                             uint32_t ntiles, uint64_t *__restrict__ kout,
-                                                             uint32_t *__restrict__ vout, uint8_t *__restrict__ nd) {
-    constexpr int TILE = T * I, RUN = TILE >> R;
-    const TileWalk walk(ntiles);
-    const uint64_t bsz = n >> R;
-    for (uint32_t t = walk.first; t < walk.end; t += walk.step) {
-        const uint64_t P0 = (uint64_t)t * TILE;
-        const uint32_t x = reinterpret_cast<const uint32_t *>(sba + P0)[threadIdx.x];  // (the tile's bytes)
-#pragma unroll 4
-        for (int g = 0; g < I; ++g) {
-            const uint32_t s = threadIdx.x + g * T, d = s / RUN, j = s - d * RUN;
-            const uint64_t o = min((uint64_t)d * bsz + (uint64_t)t * RUN + j, n - 1);
-            const uint64_t h = (P0 + s + (x & 1u)) * 0x9E3779B97F4A7C15ull;  // distinct keys, uniform digits
-            kout[o] = h;
-            vout[o] = (uint32_t)(P0 + s);
-            nd[o] = (uint8_t)(h >> 49);
-        }
-    }
-}
-
-// TIMING EXPERIMENTS ONLY (GKM_EXP_L0=v, wrong output): the scatter floor above with each lane
-// writing 4 consecutive slots of one run by vector stores (two 16-byte stores of keys, one of starts,
-// one 4-byte store of digits) -- how much of the floor is the store width rather than the stream?
-template <int T, int I, int R>
-__global__ __launch_bounds__(T) void l0_scatter_floor4_kernel(const uint8_t *__restrict__ sba, uint64_t n,
-                                                              uint32_t ntiles, uint64_t *__restrict__ kout,
-                                                              uint32_t *__restrict__ vout, uint8_t *__restrict__ nd) {
-    constexpr int TILE = T * I, RUN = TILE >> R;
-    static_assert(RUN % 4 == 0 && I % 4 == 0, "whole 4-slot groups per run");
-    const TileWalk walk(ntiles);
-    const uint64_t bsz = (n >> R) & ~3ull;
-    for (uint32_t t = walk.first; t < walk.end; t += walk.step) {
-        const uint64_t P0 = (uint64_t)t * TILE;
-        const uint32_t x = reinterpret_cast<const uint32_t *>(sba + P0)[threadIdx.x];
-#pragma unroll 2
-        for (int g = 0; g < I / 4; ++g) {
-            const uint32_t s = 4 * (threadIdx.x + g * T), d = s / RUN, j = s - d * RUN;
-            const uint64_t o = min((uint64_t)d * bsz + (uint64_t)t * RUN + j, (n - 4) & ~3ull);
-            uint64_t h[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) h[u] = (P0 + s + u + (x & 1u)) * 0x9E3779B97F4A7C15ull;
-            uint4 *k4 = reinterpret_cast<uint4 *>(kout + o);
-            k4[0] = make_uint4((uint32_t)h[0], (uint32_t)(h[0] >> 32), (uint32_t)h[1], (uint32_t)(h[1] >> 32));
-            k4[1] = make_uint4((uint32_t)h[2], (uint32_t)(h[2] >> 32), (uint32_t)h[3], (uint32_t)(h[3] >> 32));
-            reinterpret_cast<uint4 *>(vout + o)[0] =
-                make_uint4((uint32_t)(P0 + s), (uint32_t)(P0 + s + 1), (uint32_t)(P0 + s + 2), (uint32_t)(P0 + s + 3));
-            reinterpret_cast<uint32_t *>(nd + o)[0] = (uint32_t)(h[0] >> 49 & 0xFF) | (uint32_t)(h[1] >> 49 & 0xFF) << 8 |
-                                                      (uint32_t)(h[2] >> 49 & 0xFF) << 16 | (uint32_t)(h[3] >> 49 & 0xFF) << 24;
-        }
-    }
-}
-
-// Wide L0 partition (R = 10 or 11 bits; 2-bit keys of one word, forward, no profile): the
+// Wide L0 partition (R = 10 or 11 bits; 2-bit keys of one word, forward): the
 // position-staged, software-pipelined scheme of msd0_pipe_kernel with a digit space the 7-bit one
 // cannot hold -- per-wave u16 counters, two per word (rank_atomic16), K = RADIX / T digits per
 // thread in the scan, K tile offsets per thread.  With the level pass behind it, 11 + 8 bits leave
@@ -807,14 +722,13 @@ __global__ __launch_bounds__(T) void msd0_wide_kernel(L0Args a, Dig d0, const ui
 // Key-range shard select (gk_shard_sort_range)
 // ---------------------------------------------------------------------------------------------
 // A rank scans the WHOLE sequence and keeps the k-mers whose L0 digit lies in its range -- about
-// 1/N of them -- writing them contiguously in position order.  Two light streaming passes over
-// 4096-position tiles (small LDS and registers, so several workgroups per CU overlap their loads):
-//   STORE = false  kept k-mers per tile -> tile_cnt[t]          (then an exclusive scan)
-//   STORE = true   each wave compacts its kept k-mers with one ballot per row; the kept lanes of
-//                  a row store to consecutive addresses from tile_off[t]
+// 1/N of them -- in position order.  One light streaming pass over 4096-position tiles (small LDS
+// and registers, so several workgroups per CU overlap their loads): each wave compacts its kept
+// k-mers -- the forward 2-bit keys from 8-position windows per lane, the others with one ballot per
+// row of 64 positions -- and stores them to consecutive addresses.
 // Stable: tiles, waves, rows and lanes follow positions.  The kept k-mers then go through the
-// ordinary MSD levels as one bucket (the store pass writes their L0 digit bytes, so the first
-// level counts 1 byte per k-mer).  A tile is kSR rounds of 4096 positions (512 per wave per round):
+// ordinary MSD levels as one bucket (the pass writes their L0 digit bytes, so the first level
+// counts 1 byte per k-mer).  A tile is kSR rounds of 4096 positions (512 per wave per round):
 // one load of the tile's bytes (or packed words) per kSR rounds keeps more bytes in flight per
 // workgroup than one 4096-position tile did.
 #ifndef GKM_SEL_ROUNDS
@@ -825,12 +739,12 @@ constexpr int kSRound = kST * kSI;                       // 4096 positions per r
 constexpr int kSTile = kSRound * kSR;                    // positions per tile
 constexpr int kSW = kST / 64;                            // waves per tile
 
-// MODE 0 / 1 are the two passes above.  MODE 2 is a single pass: workgroup w walks its own chunk of
-// tpw consecutive tiles and appends its kept k-mers at a running offset into its own region of
-// the output, [t0 * kSTile, (t0 + tpw) * kSTile) (room for every position of the chunk, so no
-// count pass is needed); wave_cnt[w] receives the chunk's kept count.  The regions, in workgroup
-// order, are the pieces of one bucket in position order (first_level_from_pieces).
-template <int BITS, bool CANON, int MODE>
+// Workgroup w walks its own chunk of tpw consecutive tiles and appends its kept k-mers at a running
+// offset into its own region of the output, [t0 * kSTile, (t0 + tpw) * kSTile) (room for every
+// position of the chunk, so no count pass is needed); wave_cnt[w] receives the chunk's kept count.
+// The regions, in workgroup order, are the pieces of one bucket in position order
+// (first_level_from_pieces).
+template <int BITS, bool CANON>
 #ifndef GKM_SEL_MINW
 #define GKM_SEL_MINW 1
 #endif
@@ -838,17 +752,15 @@ template <int BITS, bool CANON, int MODE>
 // for; the canonical ones would spill to scratch)
 __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_kernel(L0Args a, Dig d0, uint32_t ntiles, uint32_t tpw,
                                                           uint32_t *__restrict__ wave_cnt,
-                                                          const uint32_t *__restrict__ wave_off,
                                                           uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
                                                           uint8_t *__restrict__ nd_out) {
-    constexpr bool STORE = MODE != 0;
     using P = L0Pack<BITS, kSTile>;
     // per-wave staging of the kept positions (tile-relative u16; the key is re-derived from the
     // tile's codes when it is stored): 512 slots + one dump slot per lane for the positions not
     // kept, so the staging writes need no branch.  (Staged as (key, start), 48 KB, the kernel fit
     // 3 workgroups per CU and its divergent staging loop cost more scalar than vector work.)
     constexpr int kSlots = 512 + 64;
-    constexpr int kStage = STORE ? kSW * kSlots : 1;
+    constexpr int kStage = kSW * kSlots;
     __shared__ uint64_t s_code[P::kCodeWords];
     __shared__ uint32_t s_dol[P::kGroups];
     __shared__ uint8_t s_lut4[256];
@@ -856,23 +768,21 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
     __shared__ uint32_t s_wtot[2][kSW];  // per round parity (a round's barrier orders the reuse)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 256) s_lut4[tid] = c_code4_msd[tid];
-    // tiles of this workgroup: a strided walk (MODE 0 / 1) or a chunk (MODE 2)
-    const uint32_t tfirst = MODE == 2 ? blockIdx.x * tpw : blockIdx.x;
-    const uint32_t tend = MODE == 2 ? min(tfirst + tpw, ntiles) : ntiles;
-    const uint32_t tstep = MODE == 2 ? 1u : gridDim.x;
-    const uint64_t region = (uint64_t)tfirst * kSTile;  // MODE 2: this chunk's output region
-    uint64_t run = 0;                                   // MODE 2: kept so far in the chunk
+    // tiles of this workgroup: its chunk
+    const uint32_t tfirst = blockIdx.x * tpw;
+    const uint32_t tend = min(tfirst + tpw, ntiles);
+    const uint64_t region = (uint64_t)tfirst * kSTile;  // this chunk's output region
+    uint64_t run = 0;                                   // kept so far in the chunk
     uint64_t rr[L0Units<BITS, kSTile, kST>::kPer];
     if (tfirst < tend) l0_load<BITS, kSTile, kST>(a, a.lo + (uint64_t)tfirst * kSTile, rr);
-    for (uint32_t t = tfirst; t < tend; t += tstep) {
+    for (uint32_t t = tfirst; t < tend; ++t) {
         const uint64_t P0 = a.lo + (uint64_t)t * kSTile;
         __syncthreads();  // the LUT; the previous tile's codes and wave totals have been read
         l0_pack<BITS, kSTile, kST>(rr, s_code, s_dol, s_lut4, a.acgt_only, a.pk_code != nullptr);
         __syncthreads();
         // the next tile's bytes fly while this one is processed
-        if (t + tstep < tend) l0_load<BITS, kSTile, kST>(a, P0 + (uint64_t)tstep * kSTile, rr);
-        // MODE 2: the wave's output offset from the kept counts of the tile's waves (block-uniform
-        // call: both paths below reach it)
+        if (t + 1 < tend) l0_load<BITS, kSTile, kST>(a, P0 + (uint64_t)kSTile, rr);
+        // the wave's output offset from the kept counts of the tile's waves (block-uniform call)
         auto chunk_offset = [&](uint32_t wcount, int r) -> uint64_t {
             if (lane == 0) s_wtot[r & 1][wave] = wcount;
             __syncthreads();
@@ -887,54 +797,20 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
             run += tot;
             return o;
         };
-        bool win = BITS == 2;
-        // canonical: the count pass takes the digits from windows in a tile without stops; the store
-        // passes keep the row layout below (a per-lane loop over the kept positions' canonical keys
-        // was slower: 11.9 against 8.3 ms per C5 rank at N = 8).  Both visit a wave's 512 positions
-        // in position order, so their per-wave counts and offsets agree.
-        if constexpr (BITS == 2 && CANON) {
-            if (STORE) win = false;
-            uint32_t anystop = 0;
-            for (int j = tid; j < P::kGroups; j += kST) anystop |= s_dol[j];
-            win = win && __syncthreads_or(anystop != 0) == 0 && P0 + kSTile <= a.hi && d0.mask == 0x7Fu &&
-                  (int)d0.shift == a.total_bits - 7 && a.symbols >= (a.own_bits + 1) / 2 && a.own_bits <= a.total_bits;
-        }
         for (int r = 0; r < kSR; ++r) {
             const uint32_t R0 = r * kSRound;                       // the round's first tile position
-            const uint64_t wslot = ((uint64_t)t * kSR + r) * kSW + wave;
-            if (BITS == 2 && win) {
-                // 8 consecutive positions per thread (Win8)
+            // forward 2-bit keys: 8 consecutive positions per thread (Win8).  Canonical keys keep the
+            // row layout below (a per-lane loop over the kept positions' canonical keys was slower:
+            // 11.9 against 8.3 ms per C5 rank at N = 8)
+            if constexpr (BITS == 2 && !CANON) {
                 const uint32_t q0 = R0 + tid * 8;
-                Win8 win8{};
-                uint32_t keepm = 0;
-                if constexpr (!CANON) {
-                    win8 = win8_load(s_code, s_dol, q0);
-                    uint32_t dig[8];
-                    keepm = win8_keep(win8, a, d0, (int64_t)a.hi - (int64_t)(P0 + q0), s_dol, q0, dig);
-                } else {  // the smaller of the forward and reverse-complement top own_bits bits
-                    // (msd0_count_kernel): the reverse complement's first ns symbols are the complement
-                    // of the k-mer's last ns symbols, reversed
-                    const int ob = a.own_bits, ns = (ob + 1) >> 1;
-                    const uint64_t tf = win32_at(s_code, q0), tr = win32_at(s_code, q0 + a.symbols - ns);
-                    const uint32_t om = (1u << ob) - 1;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const uint32_t f = (uint32_t)(tf >> (64 - ob - 2 * i)) & om;
-                        const uint32_t v = (uint32_t)(tr >> (64 - 2 * ns - 2 * i)) & ((1u << (2 * ns)) - 1);
-                        const uint32_t r = (uint32_t)(__builtin_bitreverse64(~(uint64_t)v) >> (64 - 2 * ns));
-                        // bitreverse flips each pair's bit order too: swap the bits of every pair back
-                        const uint32_t rr = ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
-                        keepm |= (l0_owned(min(f, rr >> (2 * ns - ob)), a) ? 1u : 0u) << i;
-                    }
-                }
+                const Win8 win8 = win8_load(s_code, s_dol, q0);
+                uint32_t dig[8];
+                const uint32_t keepm = win8_keep(win8, a, d0, (int64_t)a.hi - (int64_t)(P0 + q0), s_dol, q0, dig);
                 const uint32_t cnt = (uint32_t)__popc(keepm);
                 const uint32_t incl = wave_incl_scan(cnt);
                 const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-                if (!STORE) {
-                    if (lane == 63) wave_cnt[wslot] = incl;
-                    continue;
-                }
-                const uint64_t o = MODE == 2 ? chunk_offset(total, r) : (uint64_t)wave_off[wslot];
+                const uint64_t o = chunk_offset(total, r);
                 // stage the wave's kept positions in position order, then store the k-mers as one
                 // coalesced run
                 uint16_t *sp = s_spos + wave * kSlots;
@@ -950,15 +826,12 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
                 for (uint32_t e = lane; e < total; e += 64) {
                     const uint32_t p = sp[e];
-                    const uint64_t k = CANON ? l0_key_of<2, true>(s_code, p, a.total_bits, a.symbols)
-                                             : l0_key<2>(s_code, p, a.total_bits);
+                    const uint64_t k = l0_key<2>(s_code, p, a.total_bits);
                     kout[o + e] = k;
                     vout[o + e] = (uint32_t)(P0 + p);
                     nd_out[o + e] = (uint8_t)dg_of(k, d0);
                 }
-                continue;
-            }
-            {
+            } else {
                 // one ballot per row of 64 positions
                 const uint32_t wbase = R0 + wave * (kSI * 64);
                 uint64_t key[kSI];
@@ -974,11 +847,7 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
                     kept += (uint32_t)__popcll(m);
                     keepm |= (keep ? 1u : 0u) << i;
                 }
-                if (!STORE) {
-                    if (lane == 0) wave_cnt[wslot] = kept;
-                    continue;
-                }
-                const uint64_t base = MODE == 2 ? chunk_offset(kept, r) : (uint64_t)wave_off[wslot];
+                const uint64_t base = chunk_offset(kept, r);
 #pragma unroll
                 for (int i = 0; i < kSI; ++i) {
                     if ((keepm >> i) & 1u) {
@@ -991,7 +860,7 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
             }
         }  // rounds
     }
-    if (MODE == 2 && tid == 0 && blockIdx.x * tpw < ntiles) wave_cnt[blockIdx.x] = (uint32_t)run;
+    if (tid == 0 && blockIdx.x * tpw < ntiles) wave_cnt[blockIdx.x] = (uint32_t)run;
 }
 
 // Key-range select from the packed copy, SWAR (round 6): forward 2-bit keys of <= 32 symbols whose
@@ -999,7 +868,7 @@ __global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_ker
 // stops).  No LDS tile, no barrier: each WAVE walks its own chunk of gpw consecutive 32-position
 // groups, 64 groups (2,048 positions) per step, one group per lane, and appends its kept k-mers at
 // a running offset into its own region of the output, [first group * 32, + gpw * 32) -- the pieces
-// of one bucket in position order, as the workgroup chunks of msd0_select_kernel<..., 2> are.
+// of one bucket in position order, as the workgroup chunks of msd0_select_kernel are.
 // Per lane and group (w = the group's codes, x2 = the top half of the next group's codes):
 //   ownership digit of position j = the top own_bits bits of the 32-bit window at bit 2 j of
 //   w:x2 (one funnel shift); the range test is one subtract and one compare against the range
@@ -2410,177 +2279,6 @@ __global__ __launch_bounds__(64, MINW) void msd_wave_kernel(const uint2 *__restr
     }
 }
 
-// TIMING EXPERIMENTS ONLY (GKM_EXP_WAVECOPY=1, wrong output): the wave kernel's memory traffic
-// without its ranking -- the same list walk, loads (compact entries unpacked) and software
-// pipelining, then keys, starts and head flags stored straight from registers in load order.
-// Its time is the floor of msd_wave_kernel's bucket-granular access pattern.
-// HS: head flags stored per element (0), per aligned 4-flag chunk as one dword (1, edge chunks
-// per byte), or not at all (2) -- the store pattern's share of the floor
-template <int I, int MINW, int HS = 0>
-__global__ __launch_bounds__(64, MINW) void msd_wave_copy_kernel(const uint2 *__restrict__ list, uint32_t count, int B,
-                                                           uint64_t *k0, uint32_t *v0, const uint64_t *k1,
-                                                           const uint32_t *v1, uint8_t *__restrict__ heads,
-                                                           const uint64_t *__restrict__ cpref,
-                                                           const uint8_t *__restrict__ cnd) {
-    const int lane = threadIdx.x;
-    uint32_t idx = blockIdx.x, lend = count, lstep = gridDim.x;
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-        const uint32_t x = blockIdx.x & 7;
-        idx = (uint32_t)((uint64_t)count * x / 8) + (blockIdx.x >> 3);
-        lend = (uint32_t)((uint64_t)count * (x + 1) / 8);
-        lstep = gridDim.x >> 3;
-    }
-    if (idx >= lend) return;
-    uint2 e, en;
-    uint64_t pf, pfn;
-    uint64_t key[I], a[I];
-    uint32_t val[I], b[I];
-    wave_entry(list, cpref, idx, e, pf);
-    wave_load<I>(e, pf, lane, k0, k1, v0, v1, cnd, a, b);
-    en = e;
-    pfn = pf;
-    if (idx + lstep < lend) wave_entry(list, cpref, idx + lstep, en, pfn);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (;;) {
-        const uint64_t st = e.x;
-        const uint32_t len = e.y >> 8;
-        const int hi0 = (e.y >> 1) & 127;
-        const bool cmp = (pf & kCompact) != 0;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            key[i] = cmp ? compact_key(pf, hi0, B, b[i] & 0xFFu, (uint32_t)(a[i] >> 32)) : a[i];
-            val[i] = cmp ? (uint32_t)a[i] : b[i];
-        }
-        uint2 enn = en;
-        uint64_t pfnn = pfn;
-        if (idx + 2 * lstep < lend) wave_entry(list, cpref, idx + 2 * lstep, enn, pfnn);
-        wave_load<I>(en, pfn, lane, k0, k1, v0, v1, cnd, a, b);
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint32_t j = min((uint32_t)(i * 64 + lane), len - 1);
-            gmem(k0)[st + j] = key[i];
-            gmem(v0)[st + j] = val[i];
-            if (HS == 0) gmem(heads)[st + j] = 1;
-        }
-        if (HS == 1) {
-            const uint64_t a0 = st & ~3ull, end = st + len;
-#pragma unroll
-            for (int r = 0; r < (64 * I + 8) / 256 + 1; ++r) {
-                const uint64_t p = a0 + 4ull * (r * 64 + lane);
-                if (p >= end) continue;
-                if (p >= st && p + 4 <= end) {
-                    gmem(reinterpret_cast<uint32_t *>(heads + p))[0] = 0x01010101u;
-                } else {
-                    for (int t = 0; t < 4; ++t)
-                        if (p + t >= st && p + t < end) gmem(heads)[p + t] = 1;
-                }
-            }
-        }
-        idx += lstep;
-        if (idx >= lend) break;
-        e = en;
-        pf = pfn;
-        en = enn;
-        pfn = pfnn;
-    }
-}
-
-// TIMING EXPERIMENTS ONLY (GKM_EXP_WAVECOPY=2): the copy-only variant with the loads issued two
-// buckets ahead instead of one -- does more memory in flight per wave move the floor?
-template <int I, int MINW>
-__global__ __launch_bounds__(64, MINW) void msd_wave_copy2_kernel(const uint2 *__restrict__ list, uint32_t count, int B,
-                                                            uint64_t *k0, uint32_t *v0, const uint64_t *k1,
-                                                            const uint32_t *v1, uint8_t *__restrict__ heads,
-                                                            const uint64_t *__restrict__ cpref,
-                                                            const uint8_t *__restrict__ cnd) {
-    const int lane = threadIdx.x;
-    uint32_t idx = blockIdx.x, lend = count, lstep = gridDim.x;
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-        const uint32_t x = blockIdx.x & 7;
-        idx = (uint32_t)((uint64_t)count * x / 8) + (blockIdx.x >> 3);
-        lend = (uint32_t)((uint64_t)count * (x + 1) / 8);
-        lstep = gridDim.x >> 3;
-    }
-    if (idx >= lend) return;
-    uint2 e0, e1, e2;
-    uint64_t p0, p1, p2;
-    uint64_t a0[I], a1[I];
-    uint32_t b0[I], b1[I];
-    wave_entry(list, cpref, idx, e0, p0);
-    e1 = e0; p1 = p0;
-    if (idx + lstep < lend) wave_entry(list, cpref, idx + lstep, e1, p1);
-    wave_load<I>(e0, p0, lane, k0, k1, v0, v1, cnd, a0, b0);
-    wave_load<I>(e1, p1, lane, k0, k1, v0, v1, cnd, a1, b1);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (;;) {
-        const uint64_t st = e0.x;
-        const uint32_t len = e0.y >> 8;
-        const int hi0 = (e0.y >> 1) & 127;
-        const bool cmp = (p0 & kCompact) != 0;
-        uint64_t key[I];
-        uint32_t val[I];
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            key[i] = cmp ? compact_key(p0, hi0, B, b0[i] & 0xFFu, (uint32_t)(a0[i] >> 32)) : a0[i];
-            val[i] = cmp ? (uint32_t)a0[i] : b0[i];
-        }
-        e2 = e1; p2 = p1;
-        if (idx + 2 * lstep < lend) wave_entry(list, cpref, idx + 2 * lstep, e2, p2);
-        wave_load<I>(e2, p2, lane, k0, k1, v0, v1, cnd, a0, b0);  // two buckets ahead
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint32_t j = min((uint32_t)(i * 64 + lane), len - 1);
-            gmem(k0)[st + j] = key[i];
-            gmem(v0)[st + j] = val[i];
-            gmem(heads)[st + j] = 1;
-        }
-        idx += lstep;
-        if (idx >= lend) break;
-        // rotate: bucket 1 becomes current (its loads were issued a bucket ago)
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint64_t ta = a0[i];
-            a0[i] = a1[i];
-            a1[i] = ta;
-            const uint32_t tb = b0[i];
-            b0[i] = b1[i];
-            b1[i] = tb;
-        }
-        e0 = e1; p0 = p1;
-        e1 = e2; p1 = p2;
-    }
-}
-
-// TIMING EXPERIMENTS ONLY (GKM_EXP_WAVECOPY=5, wrong output): the wave stage's bytes as one plain
-// coalesced stream over the whole array -- 9 B in (compact word + digit byte), 13 B out (key,
-// start, head) per element; each wave takes 512 consecutive elements per step, every load and
-// store instruction covering one contiguous 512-B or 1-KiB piece -- the streaming floor of the
-// stage's traffic, against the bucket-granular floor of msd_wave_copy_kernel
-__global__ __launch_bounds__(256) void stream_copy_kernel(uint64_t n, const uint64_t *__restrict__ k1,
-                                                          const uint8_t *__restrict__ nd, uint64_t *__restrict__ k0,
-                                                          uint32_t *__restrict__ v0, uint8_t *__restrict__ heads) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wid = (blockIdx.x * 256ull + threadIdx.x) >> 6, nw = gridDim.x * 4ull;
-    for (uint64_t blk = wid; blk < n / 512; blk += nw) {
-        const uint64_t e0 = blk * 512;
-        const uint4 *ks = reinterpret_cast<const uint4 *>(k1 + e0);
-        uint4 kv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) kv[j] = ks[j * 64 + lane];
-        const uint2 d = reinterpret_cast<const uint2 *>(nd + e0)[lane];
-        uint4 *ko = reinterpret_cast<uint4 *>(k0 + e0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ko[j * 64 + lane] = make_uint4(kv[j].y ^ d.x, kv[j].x, kv[j].w, kv[j].z);
-        uint4 *vo = reinterpret_cast<uint4 *>(v0 + e0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            vo[j * 64 + lane] = make_uint4(kv[2 * j].x, kv[2 * j].z, kv[2 * j + 1].x, kv[2 * j + 1].z);
-        reinterpret_cast<uint2 *>(heads + e0)[lane] = make_uint2(d.y | 0x01010101u, d.x);
-    }
-}
-
-static bool exp_wave_copy() { return exp_opt("GKM_EXP_WAVECOPY") != nullptr; }
-
 // one round's lists, copied to device memory for the wave kernels
 __global__ void lists_store_kernel(Lists L, Lists *__restrict__ dst) { *dst = L; }
 
@@ -2982,37 +2680,13 @@ static unsigned cu_count(gk_ctx *c) {
     return (unsigned)(cus / 8 * 8);
 }
 
-// Packing is opt-in (GKM_PACK=1): measured on MI355X, the L0 partition got slower reading packed
-// words (17.8 vs 16.4 ms at C3) and the key-range passes gained less than the 0.8 ms packing costs.
-// tuning only (A/B runs): GKM_SELECT_2PASS=1 selects a key-range shard's k-mers by a count pass,
-// a scan and a store pass (the single chunked pass is the default)
-static bool select_two_pass() {
-    static const bool v = opt("GKM_SELECT_2PASS") != nullptr;
-    return v;
-}
-
-// tuning only (A/B runs): GKM_XCD_WALK_OFF=1 gives the wave kernels a grid that is not a multiple
-// of 8 (plain strided walk of the bucket list)
-static bool xcd_walk_off() {
-    static const bool v = opt("GKM_XCD_WALK_OFF") != nullptr;
-    return v;
-}
-
 // tuning only (A/B runs): GKM_NO_COMPACT=1 keeps 64-bit keys in every level's output
 static bool no_compact() { return opt("GKM_NO_COMPACT") != nullptr; }  // (read per level: tests flip it)
 
-// timing only: GKM_L0_PROF=1 times the phases of the 2-bit L0 partition (tools)
-static bool l0_prof() {
-    static const bool v = exp_opt("GKM_L0_PROF") != nullptr;
-    return v;
-}
-
-static bool use_pack() {
-    static const bool on = opt("GKM_PACK") != nullptr;
-    return on;
-}
-
-// the packed copy of c->sba (pack2_kernel) over the whole padded array, for ACGT sequences
+// the packed copy of c->sba (pack2_kernel) over the whole padded array, for ACGT sequences: only
+// where the transfer left no resident packed copy and the pass needs one (the starts-only shard
+// sort).  Packing before every sort did not pay: the L0 partition got slower reading packed words
+// (17.8 vs 16.4 ms at C3) and the key-range passes gained less than the 0.8 ms the packing costs
 static int pack_sequence(gk_ctx *c, const uint64_t **code, const uint32_t **dol) {
     const uint64_t nwords = (c->sba_len + kSbaPad) / 32;  // sba_cap >= sba_len + kSbaPad
     uint64_t *pc;
@@ -3028,7 +2702,6 @@ static int pack_sequence(gk_ctx *c, const uint64_t **code, const uint32_t **dol)
     timer_end(c, slot);
     *code = pc;
     *dol = pd;
-    c->pk_fresh = true;
     return GK_OK;
 }
 
@@ -3077,7 +2750,7 @@ struct MsdDriver {
     bool nd_ready = false, nd_next = true;
     // packed-pair levels (MODE 5): the level before a compact one writes 10-byte (key bits below
     // the sorted ones, start) pairs + the digit byte instead of 12-byte (key, start) + digit; the
-    // compact level reads them (IN79).  allow_c79: msd_sort's own levels (GKM_NO_PAIRS=1: off)
+    // compact level reads them (IN79).  allow_c79: msd_sort's own levels
     bool allow_c79 = false, c79_in = false, c79_out = false;
     // the packed L0 (P88, msd0_pipe_kernel): its output is (digit byte, packed pair) in nd_l0 /
     // lo16_l0 / keys; p88_in: the next level reads it (p88_wanted: msd_sort's decision)
@@ -3234,41 +2907,9 @@ struct MsdDriver {
             hipLaunchKernelGGL((msd0_count_kernel<BITS, kP0T / 4, kP0I * 4, R, CANON>),
                                dim3(std::min<unsigned>(nt0, cus * per_cu)), dim3(kP0T / 4), 0, c->stream, a, d0,
                                tile_hist, nt0);
-        }
-        else if (BITS == 2 && R == 7 && !CANON && !P88 && l0_prof())
-            l0_prof_launch<ND>(a, d0, kout, vout, nt, sink, ndg);
-        else
-            hipLaunchKernelGGL((msd0_pipe_kernel<BITS, kP0T, kP0I, R, ND, CANON, false, P88, OWN>), dim3(pgrid),
-                               dim3(kP0T), 0, c->stream, a, d0, tile_hist, kout, vout, nt, sink, ndg);
-    }
-
-    // timing only (GKM_L0_PROF=1): the L0 partition with per-phase clocks, printed to stderr
-    template <bool ND>
-    void l0_prof_launch(L0Args a, Dig d0, uint64_t *kout, uint32_t *vout, uint32_t nt, uint64_t sink,
-                        const NextDigits &ndg) {
-#ifndef GKM_EXPERIMENTS
-        (void)a, (void)d0, (void)kout, (void)vout, (void)nt, (void)sink, (void)ndg;  // (timing builds only)
-#else
-        unsigned long long *pr = nullptr;
-        if (scratch(c, "l0_prof", 2 * kL0Phases, &pr) != hipSuccess) return;
-        hipMemsetAsync(pr, 0, 16 * kL0Phases, c->stream);
-        a.prof = pr;
-        hipLaunchKernelGGL((msd0_pipe_kernel<2, kP0T, kP0I, 7, ND, false, true>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                           a, d0, tile_hist, kout, vout, nt, sink, ndg);
-        unsigned long long h[2 * kL0Phases];
-        hipMemcpyAsync(h, pr, 16 * kL0Phases, hipMemcpyDeviceToHost, c->stream);
-        hipStreamSynchronize(c->stream);
-        static const char *names[kL0Phases] = {"pack+load", "top-stores", "bar1", "clean", "rank+stores",
-                                               "bar2", "scan+stores", "staging+stores", "bar5"};
-        for (int w = 0; w < 2; ++w) {
-            unsigned long long tot = 0;
-            for (int k = 0; k < kL0Phases; ++k) tot += h[w * kL0Phases + k];
-            std::fprintf(stderr, "[l0prof] wave %s:", w ? "last" : "first");
-            for (int k = 0; k < kL0Phases; ++k)
-                std::fprintf(stderr, " %s %.1f%%", names[k], tot ? 100.0 * h[w * kL0Phases + k] / tot : 0.0);
-            std::fprintf(stderr, " (ticks per tile: %.0f)\n", (double)tot / std::max<uint32_t>(nt, 1));
-        }
-#endif
+        } else
+            hipLaunchKernelGGL((msd0_pipe_kernel<BITS, kP0T, kP0I, R, ND, CANON, P88, OWN>), dim3(pgrid), dim3(kP0T),
+                               0, c->stream, a, d0, tile_hist, kout, vout, nt, sink, ndg);
     }
 
     template <bool CANON>
@@ -3433,7 +3074,7 @@ struct MsdDriver {
         // exchange, so they do not)
         // (a starts-only shard send has no key output: kout == nullptr, which a context whose key
         // buffers are not allocated yet must not mistake for one of them)
-        const bool with_nd = kout && (kout == c->keys[0] || kout == c->keys[1]) && !opt("GKM_L0_NO_ND");  // (tuning knob)
+        const bool with_nd = kout && (kout == c->keys[0] || kout == c->keys[1]);
         NextDigits ndg{dig_at(B, w0, width(1)), nullptr};
         if (with_nd && p88) {  // the packed L0: digit bytes and low start bits in the free start buffer
             p88_place(vout == c->vals[0] ? 0 : 1);
@@ -3445,32 +3086,7 @@ struct MsdDriver {
             GK_TRY_HIP(c, scratch(c, "msd_nd", n + 64, &nd));
             ndg.out = nd;
         }
-        // timing experiments only (wrong output): GKM_EXP_L0=1 the scatter floor at 2^7 runs per tile,
-        // =4 / 5 / 6 / 8 at 2^R runs (the same bytes in fewer or more write streams), =v at 2^7 runs
-        // with 4-slot vector stores
-        static const char *exp_l0 = exp_opt("GKM_EXP_L0");
-        const int exp_r = exp_l0 ? (exp_l0[0] == '1' || exp_l0[0] == 'v' ? 7 : exp_l0[0] - '0') : 0;
-        if (exp_r && with_nd && w0 == 7) {
-            if (exp_r == 4)
-                hipLaunchKernelGGL((l0_scatter_floor_kernel<kP0T, kP0I, 4>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-            else if (exp_r == 5)
-                hipLaunchKernelGGL((l0_scatter_floor_kernel<kP0T, kP0I, 5>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-            else if (exp_r == 6)
-                hipLaunchKernelGGL((l0_scatter_floor_kernel<kP0T, kP0I, 6>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-            else if (exp_l0[0] == 'v')
-                hipLaunchKernelGGL((l0_scatter_floor4_kernel<kP0T, kP0I, 7>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-            else if (exp_r == 8)
-                hipLaunchKernelGGL((l0_scatter_floor_kernel<kP0T, kP0I, 8>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-            else
-                hipLaunchKernelGGL((l0_scatter_floor_kernel<kP0T, kP0I, 7>), dim3(pgrid), dim3(kP0T), 0, c->stream,
-                                   c->sba, count, (uint32_t)l0_tiles, kout, vout, nd);
-        } else
-            l0_dispatch(false, w0, with_nd, l0a, d0, (unsigned)l0_tiles, kout, vout, (uint32_t)l0_tiles, count, ndg);
+        l0_dispatch(false, w0, with_nd, l0a, d0, (unsigned)l0_tiles, kout, vout, (uint32_t)l0_tiles, count, ndg);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
         nd_ready = with_nd;
@@ -3480,10 +3096,10 @@ struct MsdDriver {
 
     // the packed L0 pays when the level behind it writes packed pairs itself (it reads the packed
     // form, INP = 2): the same prediction level_pass makes at L1 from the mean bucket sizes, with the
-    // L1 digit being the digit byte (8 bits).  GKM_NO_P88=1: off; GKM_TEST_P88=1 (tests): wherever
+    // L1 digit being the digit byte (8 bits).  GKM_TEST_P88=1 (tests): wherever
     // the bits fit.  C3: 62 - 7 = 55 bits after the L0, 47 of them in the pair (shi 17).
     bool p88_wanted() const {
-        if (opt("GKM_NO_P88") || !allow_c79 || ks.bits != 2 || phase != 0 || no_compact()) return false;
+        if (!allow_c79 || ks.bits != 2 || phase != 0 || no_compact()) return false;
         const int w0 = width(0), w1 = width(1), w2 = width(2), rem = B - w0;
         if ((w0 != 6 && w0 != 7 && w0 != kGR) || w1 != 8 || rem - 8 < 33 || rem - 8 > 48) return false;
         if (opt("GKM_TEST_P88")) return true;
@@ -4124,7 +3740,7 @@ struct MsdDriver {
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1)
                 per_cu = 1;
             uint64_t g = std::min<uint64_t>(cnt, (uint64_t)cus * per_cu);
-            if (g >= 8) g = xcd_walk_off() ? g - ((g & 7) == 0) : (g & ~7ull);  // the wave kernels' XCD-aware walk
+            if (g >= 8) g &= ~7ull;  // the wave kernels' XCD-aware walk
             return dim3((unsigned)g);
         };
         // wave classes: msd_wave_kernel<I, waves per SIMD, keys written>
@@ -4142,34 +3758,6 @@ struct MsdDriver {
             wave(msd_wave_kernel<4, kWaveOcc4, true, kWaveR4>, msd_wave_kernel<4, kWaveOcc4, false, kWaveR4>);
             break;
         case 1:
-            if (exp_wave_copy() && exp_opt("GKM_EXP_WAVECOPY")[0] == '2') {  // timing only
-                hipLaunchKernelGGL((msd_wave_copy2_kernel<8, kWaveOcc8>),
-                                   grid((const void *)msd_wave_copy2_kernel<8, kWaveOcc8>, 64), dim3(64), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, ci.pref, ci.nd);
-                break;
-            }
-            if (exp_wave_copy() && exp_opt("GKM_EXP_WAVECOPY")[0] == '3') {  // timing only
-                hipLaunchKernelGGL((msd_wave_copy_kernel<8, kWaveOcc8, 1>),
-                                   grid((const void *)msd_wave_copy_kernel<8, kWaveOcc8, 1>, 64), dim3(64), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, ci.pref, ci.nd);
-                break;
-            }
-            if (exp_wave_copy() && exp_opt("GKM_EXP_WAVECOPY")[0] == '4') {  // timing only
-                hipLaunchKernelGGL((msd_wave_copy_kernel<8, kWaveOcc8, 2>),
-                                   grid((const void *)msd_wave_copy_kernel<8, kWaveOcc8, 2>, 64), dim3(64), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, ci.pref, ci.nd);
-                break;
-            }
-            if (exp_wave_copy() && exp_opt("GKM_EXP_WAVECOPY")[0] == '5') {  // timing only
-                hipLaunchKernelGGL(stream_copy_kernel, dim3(cus * 8), dim3(256), 0, c->stream, n, k1, nd, k0, v0, heads);
-                break;
-            }
-            if (exp_wave_copy()) {  // timing experiments only: wrong output
-                hipLaunchKernelGGL((msd_wave_copy_kernel<8, kWaveOcc8>),
-                                   grid((const void *)msd_wave_copy_kernel<8, kWaveOcc8>, 64), dim3(64), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, ci.pref, ci.nd);
-                break;
-            }
             wave(msd_wave_kernel<8, kWaveOcc8, true, kWaveR8>, msd_wave_kernel<8, kWaveOcc8, false, kWaveR8>);
             break;
         case 2:
@@ -4181,22 +3769,11 @@ struct MsdDriver {
                                cnt, B, k0, v0, k1, v1, heads, nl, ctr, skip,
                                (uint32_t)kSmall, wkeys, ci);  // the block class keeps kSmall: 96 measured slower (A/B)
             break;
-        case 5: {
-            // (A/B: GKM_BLOCK32_T512=1 -- 512 threads x 16 keys: half the per-wave counters to
-            // zero and scan per bucket, half the waves)
-            static const bool t512 = opt("GKM_BLOCK32_T512") != nullptr;
-            if (t512)
-                hipLaunchKernelGGL((msd_local_kernel<kBT, 2 * kBI, kBR2>),
-                                   grid((const void *)msd_local_kernel<kBT, 2 * kBI, kBR2>, kBT), dim3(kBT), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, nl, ctr, skip, (uint32_t)kSmall,
-                                   wkeys, ci);
-            else
-                hipLaunchKernelGGL((msd_local_kernel<kBT2, kBI, kBR2>),
-                                   grid((const void *)msd_local_kernel<kBT2, kBI, kBR2>, kBT2), dim3(kBT2), 0,
-                                   c->stream, lst, cnt, B, k0, v0, k1, v1, heads, nl, ctr, skip, (uint32_t)kSmall,
-                                   wkeys, ci);
+        case 5:
+            hipLaunchKernelGGL((msd_local_kernel<kBT2, kBI, kBR2>),
+                               grid((const void *)msd_local_kernel<kBT2, kBI, kBR2>, kBT2), dim3(kBT2), 0, c->stream,
+                               lst, cnt, B, k0, v0, k1, v1, heads, nl, ctr, skip, (uint32_t)kSmall, wkeys, ci);
             break;
-        }
         default:
             hipLaunchKernelGGL(msd_tiny_kernel, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, lst, cnt, k0, v0, k1,
                                v1, heads, wkeys, ci, B);
@@ -4233,7 +3810,7 @@ struct MsdDriver {
                 uint64_t *k0 = c->keys[0], *k1 = c->keys[1];
                 uint32_t *v0 = c->vals[0], *v1 = c->vals[1];
                 const uint2 *lst = loc[k][g];
-                static const bool trace = opt("GKM_MSD_TRACE") != nullptr;
+                const bool trace = opt("GKM_MSD_TRACE") != nullptr;  // (read per launch: a few per sort)
                 hipEvent_t t0 = nullptr, t1 = nullptr;
                 if (trace) {
                     hipEventCreate(&t0);
@@ -4292,17 +3869,13 @@ int msd_sort(gk_ctx *c, const KeySpec &ks) {
     // L0's 49 and 41 bits do not allow (C5 219-221 -> 216.7-216.9 ms, profiles/r4/l08_ab.txt; the
     // same change made C4, 62-bit keys, 5 ms slower)
     if (ks.bits == 2 && ks.canonical && d.B == 64 && !opt("GKM_LEVEL_BITS")) d.wsched[0] = 8;
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     d.wkeys = (nphase == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;  // one-word keys end final in keys[0]
     c->msd_keys_final = d.wkeys != 0;
     timer_begin(c, "msd_total", &d.total_slot);
     int rc = d.init(c->n);
     if (rc != GK_OK) return rc;
-    if (use_pack() && c->acgt && ks.bits == 2 && !ks.acgt_only) {  // both L0 passes read the packed sequence
-        rc = pack_sequence(c, &d.pk_code, &d.pk_dol);
-        if (rc != GK_OK) return rc;
-        c->pk_fresh = false;
-    } else if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {
+    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {
         // the packed copy the transfer left beside the sba (gkm_xfer.hip): both L0 passes read 0.37 B
         // per position instead of packing the bytes in every tile.  Its stops are the non-ACGT bytes:
         // '$' on an ACGT sba, every byte that ends the ACGT-only k-mers of a mixed one (class A)
@@ -4316,14 +3889,13 @@ int msd_sort(gk_ctx *c, const KeySpec &ks) {
     // The L0's output buffer: the one that makes the last global level write buffer 1, so that the
     // finishing kernels read buffer 1 and write buffer 0 instead of rewriting buffer 0 in place
     // (levels predicted from the mean bucket size; C3: L0, L1, L2 -> L0 writes buffer 1).  A/B on
-    // one box (C3, 3 pairs): 67.3-68.3 against 67.7-68.8 ms.  GKM_L0_BUF=0/1 forces it.
+    // one box (C3, 3 pairs): 67.3-68.3 against 67.7-68.8 ms.
     int l0b = 0;
     {
         uint64_t mean = c->n >> d.width(0);
         int lev = 0;
         for (int l = 1; mean > (uint64_t)kBlockMax && l < kMaxLevels; ++l, ++lev) mean >>= d.width(l);
         l0b = 1 ^ (lev & 1);
-        if (const char *e = opt("GKM_L0_BUF")) l0b = std::atoi(e) & 1;
     }
     rc = d.run_l0(0, c->sba_len, c->keys[l0b], c->vals[l0b], c->elem_cap + 64, &found);
     if (rc != GK_OK) return rc;
@@ -4402,7 +3974,7 @@ int prefetch_plan(gk_ctx *c, uint64_t len, L0Prefetch **out) {
     p->n = len - k + 1;
     p->w0 = d.width(0);
     p->w1 = d.width(1);
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     d.n = p->n;
     p->p88 = d.p88_wanted();
     p->p88_shi = 64 - (d.B - p->w0 - 8);
@@ -4532,7 +4104,7 @@ int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks) {
     MsdDriver d(c, ks);
     d.B = ks.total_bits;
     if (d.width(0) != c->pre_w0 || d.width(1) != c->pre_w1) return msd_sort(c, ks);  // (widths changed)
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     d.wkeys = (!ks.acgt_only || c->msd_force_keys) ? 1 : 0;  // one-word keys end final in keys[0] (as msd_sort)
     c->msd_keys_final = d.wkeys != 0;
     timer_begin(c, "msd_total", &d.total_slot);
@@ -4619,7 +4191,7 @@ int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint
     d.wkeys = (nphase == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;  // one-word keys end final in keys[0]
     c->msd_keys_final = d.wkeys != 0;
     d.wsched[0] = kGR;  // pieces are kGR-bit buckets
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     timer_begin(c, "msd_total", &d.total_slot);
     int rc = d.init(c->n);
     if (rc != GK_OK) return rc;
@@ -4673,7 +4245,7 @@ int msd_sort_keys(gk_ctx *c, int total_bits) {
     MsdDriver d(c, kk);
     d.B = total_bits;
     d.wkeys = 1;
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     // digit widths: as few global levels as leave buckets of <= ~400 keys for the one-wave
     // finishing classes (1e8 keys: 6 + 6 + 6 bits, buckets of ~380), the bits spread evenly; two
     // 8-bit levels left 1.5 K-key buckets to the block-local class, which ran 3.6 ms for 1e8 keys
@@ -4744,12 +4316,7 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
     MsdDriver d(c, ks);
     d.B = ks.bits * std::min(ks.symbols, 64 / ks.bits);  // the first key word (see msd_sort)
     GK_TRY_HIP(c, msd_tables());
-    // the packed sequence is made here for the whole sba and kept for the gk_shard_sort_range
-    // that follows (one packing per key-range step)
-    if (use_pack() && c->acgt && ks.bits == 2) {
-        int rp = pack_sequence(c, &d.pk_code, &d.pk_dol);
-        if (rp != GK_OK) return rp;
-    } else if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
+    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
         d.pk_code = c->res_code;
         d.pk_dol = c->res_dol;
     }
@@ -4774,7 +4341,7 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
         const unsigned g = std::min<unsigned>(ntiles, d.cus * (unsigned)per_cu);                               \
         hipLaunchKernelGGL((own_hist_kernel<B_, C_>), dim3(g), dim3(kST), 0, c->stream, a, ntiles, gh);        \
     } while (0)
-    if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.hi > lo && !opt("GKM_RSEL_OFF")) {
+    if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.hi > lo) {
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, own_hist_rsel_kernel, kRselW * 64, 0) != hipSuccess ||
             per_cu < 1)
@@ -4805,37 +4372,20 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
     c->msd_keys_final = d.wkeys != 0;
     // packed-pair levels where the bits fit (the first level from the select's pieces has 55 bits
     // left at C3: its L1 writes the pairs)
-    d.allow_c79 = opt("GKM_NO_PAIRS") == nullptr;
+    d.allow_c79 = true;
     d.wsched[0] = range_width(ks);
     timer_begin(c, "msd_total", &d.total_slot);
     GK_TRY_HIP(c, msd_tables());
     const uint64_t L = c->sba_len;
     const uint32_t ntiles = (uint32_t)std::max<uint64_t>((L + kSTile - 1) / kSTile, 1);
-    const uint64_t nw = (uint64_t)ntiles * kSR * kSW;
     L0Args a{c->sba, 0, L, ks.symbols, d.B, ks.acgt_only};
     a.own_lo = digit_lo;
     a.own_span = digit_hi > digit_lo ? digit_hi - digit_lo : 0;
     a.own_bits = range_own_bits(ks);
-    if (use_pack() && c->acgt && ks.bits == 2) {  // this step's gk_shard_histogram's packing, or pack now
-        if (c->pk_fresh) {
-            uint64_t *pc;
-            uint32_t *pd;
-            const uint64_t nwords = (L + kSbaPad) / 32;
-            GK_TRY_HIP(c, scratch(c, "pk_code", nwords, &pc));
-            GK_TRY_HIP(c, scratch(c, "pk_dol", nwords, &pd));
-            a.pk_code = pc;
-            a.pk_dol = pd;
-        } else {
-            int rp = pack_sequence(c, &a.pk_code, &a.pk_dol);
-            if (rp != GK_OK) return rp;
-        }
-        c->pk_fresh = false;
-        d.pk_code = a.pk_code;  // (the fused L0 reads it too)
-        d.pk_dol = a.pk_dol;
-    } else if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
+    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
         a.pk_code = c->res_code;
         a.pk_dol = c->res_dol;
-        d.pk_code = c->res_code;
+        d.pk_code = c->res_code;  // (the fused L0 reads it too)
         d.pk_dol = c->res_dol;
     }
     // Fused select (round 5): when the rank keeps a large share of the k-mers, its L0 count and
@@ -4887,70 +4437,14 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
         }
     }
     const Dig d0 = dig_at(d.B, 0, d.width(0));
-    const bool two_pass = select_two_pass();
-    uint32_t *wave_cnt, *wave_off;
-    GK_TRY_HIP(c, scratch(c, "sel_wave_cnt", nw + 1, &wave_cnt));
-    GK_TRY_HIP(c, scratch(c, "sel_wave_off", nw + 1, &wave_off));
+    uint32_t *wave_cnt;
+    GK_TRY_HIP(c, scratch(c, "sel_wave_cnt", (uint64_t)ntiles + 1, &wave_cnt));
     c->n = 0;  // nothing in the buffers survives: ensure_elems copies none
     c->cur = 0;
-    // single pass: chunks of tpw tiles per workgroup, one region of tpw * kSTile elements each in
-    // keys[1] / vals[1] (room for every position: no count pass)
-    uint32_t tpw = 1, nchunk = 0;
-    auto launch = [&](int mode) {
-        uint64_t *ko = mode ? c->keys[mode == 2 ? 1 : 0] : nullptr;
-        uint32_t *vo = mode ? c->vals[mode == 2 ? 1 : 0] : nullptr;
-        uint8_t *no = mode ? d.nd : nullptr;
-        // persistent grid = the workgroups that fit at once (a second round of workgroups would
-        // start only when the first ones have walked all their tiles)
-#define GK_SEL(B_, C_, M_)                                                                                    \
-    do {                                                                                                      \
-        int per_cu = 0;                                                                                       \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msd0_select_kernel<B_, C_, M_>, kST, 0) !=  \
-                hipSuccess ||                                                                                 \
-            per_cu < 1)                                                                                       \
-            per_cu = 1;                                                                                       \
-        unsigned sgrid = std::min<unsigned>(ntiles, d.cus * (unsigned)per_cu);                                \
-        if (M_ == 2) {                                                                                        \
-            tpw = (ntiles + sgrid - 1) / sgrid;                                                               \
-            sgrid = nchunk = (ntiles + tpw - 1) / tpw;                                                        \
-        }                                                                                                     \
-        hipLaunchKernelGGL((msd0_select_kernel<B_, C_, M_>), dim3(sgrid), dim3(kST), 0, c->stream, a, d0,     \
-                           ntiles, tpw, wave_cnt, wave_off, ko, vo, no);                                      \
-    } while (0)
-#define GK_SEL_M(B_, C_)                                                                                      \
-    do {                                                                                                      \
-        if (mode == 0) GK_SEL(B_, C_, 0);                                                                     \
-        else if (mode == 1) GK_SEL(B_, C_, 1);                                                                \
-        else GK_SEL(B_, C_, 2);                                                                               \
-    } while (0)
-        if (ks.bits == 2 && ks.canonical) GK_SEL_M(2, true);
-        else if (ks.bits == 2) GK_SEL_M(2, false);
-        else if (ks.canonical) GK_SEL_M(4, true);
-        else GK_SEL_M(4, false);
-#undef GK_SEL_M
-#undef GK_SEL
-    };
     int slot;
     uint64_t found = 0;
     std::vector<uint64_t> poff, plen;
-    if (two_pass) {
-        timer_begin(c, "msd_select_count", &slot);
-        timer_units(c, slot, L);
-        launch(0);
-        GK_TRY_HIP(c, hipGetLastError());
-        GK_TRY_HIP(c, scan_u32_exclusive_pub(c, wave_cnt, nw, wave_off, &found));
-        timer_end(c, slot);
-        if (found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
-        int rc = ensure_elems(c, std::max<uint64_t>(found, 1), 1);
-        if (rc != GK_OK) return rc;
-        GK_TRY_HIP(c, scratch(c, "msd_nd", found + 64, &d.nd));
-        timer_begin(c, "msd_select", &slot);
-        timer_units(c, slot, found);
-        launch(1);
-        GK_TRY_HIP(c, hipGetLastError());
-        timer_end(c, slot);
-    } else if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.own_bits <= 32 &&
-               !opt("GKM_RSEL_OFF")) {
+    if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.own_bits <= 32) {
         // the SWAR select over the packed copy: one region per wave (msd0_rsel_kernel)
         const uint64_t ngroups = (L + 31) / 32;
         int per_cu = 0;
@@ -4999,8 +4493,30 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
         GK_TRY_HIP(c, scratch(c, "msd_nd", cap + 64, &d.nd));
         timer_begin(c, "msd_select", &slot);
         timer_units(c, slot, L);
-        launch(2);
-        const uint64_t stride = (uint64_t)tpw * kSTile;  // each chunk's region (launch sets tpw)
+        // single pass: chunks of tpw tiles per workgroup, one region of tpw * kSTile elements each in
+        // keys[1] / vals[1] (room for every position: no count pass).  Persistent grid = the
+        // workgroups that fit at once (a second round of workgroups would start only when the
+        // first ones have walked all their tiles)
+        uint32_t tpw = 1, nchunk = 0;
+#define GK_SEL(B_, C_)                                                                                         \
+    do {                                                                                                       \
+        int per_cu = 0;                                                                                        \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msd0_select_kernel<B_, C_>, kST, 0) !=       \
+                hipSuccess ||                                                                                  \
+            per_cu < 1)                                                                                        \
+            per_cu = 1;                                                                                        \
+        const unsigned sgrid = std::min<unsigned>(ntiles, d.cus * (unsigned)per_cu);                           \
+        tpw = (ntiles + sgrid - 1) / sgrid;                                                                    \
+        nchunk = (ntiles + tpw - 1) / tpw;                                                                     \
+        hipLaunchKernelGGL((msd0_select_kernel<B_, C_>), dim3(nchunk), dim3(kST), 0, c->stream, a, d0, ntiles, \
+                           tpw, wave_cnt, c->keys[1], c->vals[1], d.nd);                                       \
+    } while (0)
+        if (ks.bits == 2 && ks.canonical) GK_SEL(2, true);
+        else if (ks.bits == 2) GK_SEL(2, false);
+        else if (ks.canonical) GK_SEL(4, true);
+        else GK_SEL(4, false);
+#undef GK_SEL
+        const uint64_t stride = (uint64_t)tpw * kSTile;  // each chunk's region
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
         std::vector<uint32_t> kc(nchunk);
@@ -5026,22 +4542,12 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
     if (rc != GK_OK) return rc;
     d.nd = nd_keep;
     d.nd_ready = true;  // the select wrote the L0 digit bytes
-    if (two_pass) {
-        // the kept k-mers as one bucket [0, found) with no key bits sorted
-        uint32_t *one;
-        GK_TRY_HIP(c, scratch(c, "sel_bucket", 2, &one));
-        const uint32_t hb[2] = {0, (uint32_t)found};
-        GK_TRY_HIP(c, hipMemcpyAsync(one, hb, 8, hipMemcpyHostToDevice, c->stream));
-        rc = d.classify(1, 0, 0, 0, one, one + 1);
-        if (rc == GK_OK) rc = d.levels(0, 0, 0);
-    } else {
-        // the chunks' regions of keys[1] / vals[1] are the pieces of one bucket, in position order;
-        // the first level partitions them into [0, found) of keys[0] / vals[0]
-        const std::vector<uint32_t> pb(poff.size(), 0u);
-        rc = d.first_level_from_pieces(c->keys[1], c->vals[1], poff.data(), plen.data(), pb.data(),
-                                       (uint32_t)poff.size(), 0, 0);
-        if (rc == GK_OK) rc = d.levels(1, d.width(0), 0);
-    }
+    // the chunks' regions of keys[1] / vals[1] are the pieces of one bucket, in position order;
+    // the first level partitions them into [0, found) of keys[0] / vals[0]
+    const std::vector<uint32_t> pb(poff.size(), 0u);
+    rc = d.first_level_from_pieces(c->keys[1], c->vals[1], poff.data(), plen.data(), pb.data(), (uint32_t)poff.size(),
+                                   0, 0);
+    if (rc == GK_OK) rc = d.levels(1, d.width(0), 0);
     if (rc == GK_OK) rc = d.finish();
     for (int ph = 1; ph < nphase && rc == GK_OK; ++ph)
         rc = d.next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));

@@ -222,7 +222,10 @@ bool have_avx2() {
 
 // GKM_PACK_IMPL=scalar / avx2 / avx512 (A/B and tests); default AVX2: on the GPU box's EPYC 9575F
 // the AVX-512 packer moved 3.1 Gb in 25-29 ms against 22 ms for AVX2, 16 threads, medians of 7
-// (profiles/r5/xfer_probe.txt) -- the packing is bound by host memory, not by instructions
+// (profiles/r5/xfer_probe.txt) -- the packing is bound by host memory, not by instructions.
+// Latched at first use: the packing threads call this for every chunk, so it takes no lock there
+// and all chunks of a transfer use one packer; a process that wants another packer sets the knob
+// before its first transfer (the tests run one child process per packer).
 int pack_impl() {
     static const int v = [] {
         const char *e = opt("GKM_PACK_IMPL");

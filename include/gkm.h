@@ -141,11 +141,13 @@ int gk_alphabet_is_acgt(gk_ctx *ctx, int *is_acgt);
  * reference counterpart (the reference has no transfer). */
 int gk_resident_packed(gk_ctx *ctx, int *on);
 /* Test and tuning overrides of the library's GKM_* knobs, process-wide (no reference counterpart):
- * value NULL clears the override.  Only the operational knobs (GKM_XFER_THREADS, GKM_XFER_NUMA,
- * GKM_XFER_HYBRID, GKM_PACK_IMPL, GKM_PACK_MIN, GKM_PACK_BLOCKS, GKM_NO_RESIDENT_PACK,
- * GKM_RANK_BALLOT, GKM_PREFETCH_REGIONS, GKM_MSD_TRACE; and GKM_FASTA_CHUNK of the FASTA parser)
- * are also read from the environment; every other knob -- alternative sort paths, forced formats,
- * test-only chunk sizes -- is reachable only through this call. */
+ * value NULL clears the override.  The library keeps one table of the knobs it reads (kKnobs,
+ * gkm_capi.hip); a name that is not in it -- unknown, misspelt or retired -- is refused with
+ * GK_E_ARG.  Only the operational knobs (GKM_RANK_BALLOT, GKM_PACK_IMPL, GKM_PACK_MIN,
+ * GKM_PACK_BLOCKS, GKM_XFER_THREADS, GKM_XFER_HYBRID, GKM_XFER_NUMA, GKM_NO_RESIDENT_PACK,
+ * GKM_PREFETCH_REGIONS, GKM_MSD_TRACE, GKM_VMM_CHUNK_MB) are also read from the environment; every
+ * other knob -- alternative sort paths, forced formats, test-only chunk sizes -- is reachable only
+ * through this call.  (GKM_FASTA_CHUNK of the FASTA parser is an environment variable only.) */
 int gk_set_option(const char *name, const char *value);
 
 /* ---- enumerate / sort ------------------------------------------------------------------------ */
