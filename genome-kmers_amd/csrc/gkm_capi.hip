@@ -45,6 +45,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_TEST_PAIRS", false},      {"GKM_TEST_P88", false},        {"GKM_TEST_CHUNK_TILES", false},
     {"GKM_TEST_SCAN_CHUNK", false}, {"GKM_TEST_SEG_SCAN_MULTI", false}, {"GKM_TEST_CHECK_TILES", false},
     {"GKM_TEST_VMM_MIN_KB", false},
+    // gk_lookup (gkm_lookup.hip): forced path (bytes | keys), queries per launch, directory off (0)
+    {"GKM_LOOKUP_PATH", false},     {"GKM_LOOKUP_CHUNK", false},    {"GKM_LOOKUP_DIR", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)
@@ -392,7 +394,7 @@ int gkm::ensure_elems(gk_ctx *c, uint64_t n, int words) {
         c->elem_cap = n;
         c->key_words_cap = 0;
         c->key_words_b[0] = c->key_words_b[1] = 0;
-        c->keys_valid = false;
+        c->keys_valid = c->lookup_dir_valid = false;
     }
     if (words > c->key_words_cap) {
         for (int b = 0; b < 2; ++b) {
@@ -403,7 +405,7 @@ int gkm::ensure_elems(gk_ctx *c, uint64_t n, int words) {
             c->key_words_b[b] = words;
         }
         c->key_words_cap = words;
-        c->keys_valid = false;
+        c->keys_valid = c->lookup_dir_valid = false;
     }
     const uint64_t tiles = (n + kSortTile - 1) / kSortTile + 1;
     if (tiles * 256 > c->status_cap) {
@@ -603,6 +605,9 @@ extern "C" void gk_destroy(gk_ctx *c) {
     if (c->pre_stream) hipStreamSynchronize(c->pre_stream);
     xfer_release(c);
     if (c->hpin) hipHostFree(c->hpin);
+    if (c->lookup_pin) hipHostFree(c->lookup_pin);
+    for (hipEvent_t e : c->lookup_ev)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->pre_ev) hipEventDestroy(e);
     if (c->pre_done) hipEventDestroy(c->pre_done);
     if (c->pre_stream) hipStreamDestroy(c->pre_stream);
@@ -684,6 +689,7 @@ extern "C" int gk_set_sequence(gk_ctx *c, const uint8_t *sba, uint64_t len, cons
     }
     c->have_starts = c->sorted = c->keys_valid = c->enumerated = c->unique_valid = c->heads_valid = c->canonical = false;
     c->enum_sorted = false;
+    c->lookup_dir_valid = false;
     if (len < packed_transfer_min()) c->res_pk = false;  // (the packed transfer sets it)
     c->n = 0;
     if (h[0] & 4u) return fail(c, GK_E_ALPHABET, "Sequence contains non-allowed characters!");
@@ -759,6 +765,7 @@ extern "C" int gk_enumerate(gk_ctx *c, uint32_t min_k, uint64_t *n_out) {
     c->enumerated = true;
     c->starts_materialized = false;
     c->sorted = c->keys_valid = c->unique_valid = c->heads_valid = c->canonical = c->enum_sorted = false;
+    c->lookup_dir_valid = false;
     if (n_out) *n_out = n;
     return GK_OK;
 }
@@ -781,6 +788,7 @@ extern "C" int gk_set_start_indices(gk_ctx *c, const uint32_t *src, uint64_t n, 
     c->enumerated = false;
     c->starts_materialized = true;
     c->sorted = c->keys_valid = c->unique_valid = c->heads_valid = c->canonical = c->enum_sorted = false;
+    c->lookup_dir_valid = false;
     return GK_OK;
 }
 
@@ -1187,7 +1195,7 @@ extern "C" int gk_sort(gk_ctx *c, uint32_t max_kmer_len, uint32_t flags) {
         GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
         if (bad) return fail(c, GK_E_NO_BASES, "kmers compared were less than min_kmer_len");
     }
-    c->unique_valid = c->heads_valid = false;
+    c->unique_valid = c->heads_valid = c->lookup_dir_valid = false;
     c->enum_sorted = false;
     const bool from_enum = c->enumerated;
     // only the fixed-length forward sort of the whole enumeration uses a prefetched L0 (sort_direct)
@@ -1264,12 +1272,13 @@ extern "C" int gk_sort(gk_ctx *c, uint32_t max_kmer_len, uint32_t flags) {
     return GK_OK;
 }
 
-extern "C" int gk_copy_strands(gk_ctx *c, uint8_t *dst, uint64_t n) {
+extern "C" int gk_copy_strand_range(gk_ctx *c, uint64_t offset, uint8_t *dst, uint64_t n) {
     if (!c) return GK_E_ARG;
     pre_drop(c);  // (the k-mer buffers: a prefetched L0 does not survive)
     if (!c->sorted || !c->canonical) return fail(c, GK_E_STATE, "strands need a canonical sort (GK_SORT_CANONICAL)");
-    if (n != c->n) return fail(c, GK_E_ARG, "n differs from the k-mer count");
+    if (offset > c->n || n > c->n - offset) return fail(c, GK_E_ARG, "range outside the k-mer array");
     if (n == 0) return GK_OK;
+    if (!dst) return fail(c, GK_E_ARG, "null array");
     GK_TRY_HIP(c, hipSetDevice(c->device));
     if (int rc = materialize_starts(c)) return rc;
     KeySpec ks{};
@@ -1277,10 +1286,17 @@ extern "C" int gk_copy_strands(gk_ctx *c, uint8_t *dst, uint64_t n) {
     ks.symbols = (int)c->sort_len;
     uint8_t *d;
     GK_TRY_HIP(c, scratch(c, "strands", n, &d));
-    GK_TRY_HIP(c, launch_canon_strands(c, ks, c->vals[c->cur], n, d));
+    GK_TRY_HIP(c, launch_canon_strands(c, ks, c->vals[c->cur] + offset, n, d));
     GK_TRY_HIP(c, hipMemcpyAsync(dst, d, n, hipMemcpyDeviceToHost, c->stream));
     GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
     return GK_OK;
+}
+
+extern "C" int gk_copy_strands(gk_ctx *c, uint8_t *dst, uint64_t n) {
+    if (!c) return GK_E_ARG;
+    pre_drop(c);
+    if (c->sorted && c->canonical && n != c->n) return fail(c, GK_E_ARG, "n differs from the k-mer count");
+    return gk_copy_strand_range(c, 0, dst, n);
 }
 
 extern "C" int gk_copy_start_indices(gk_ctx *c, uint32_t *dst, uint64_t n) {
@@ -1617,6 +1633,7 @@ static int shard_sort_range_impl(gk_ctx *c, uint32_t k, uint32_t flags, uint32_t
     c->enumerated = false;
     c->starts_materialized = true;
     c->sorted = c->keys_valid = c->unique_valid = c->heads_valid = c->canonical = c->enum_sorted = false;
+    c->lookup_dir_valid = false;
     if (range_split(c, ks)) {  // mixed sba: ACGT-only k-mers by 2-bit digit, the rest by prefix
         const int ob = range_own_bits(acgt_spec(ks));
         SplitRange rg{digit_lo, digit_hi, range_prefix(digit_lo, true, ob), range_prefix(digit_hi, false, ob), (ob + 1) / 2};
@@ -1665,6 +1682,7 @@ extern "C" int gk_shard_sort(gk_ctx *c, const uint64_t *d_keys, const uint32_t *
     c->enumerated = false;
     c->starts_materialized = true;
     c->sorted = c->keys_valid = c->unique_valid = c->heads_valid = c->canonical = c->enum_sorted = false;
+    c->lookup_dir_valid = false;
     if (n > 0) {
         rc = msd_shard_sort(c, ks, starts_only ? nullptr : d_keys, d_starts, h_piece_off, h_piece_len, h_piece_bucket,
                             npieces);

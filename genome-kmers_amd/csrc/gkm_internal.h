@@ -155,6 +155,16 @@ struct gk_ctx {
     uint64_t n_unique = 0;
     bool unique_valid = false;
 
+    // gk_lookup's prefix directory over keys[cur] (gkm_lookup.hip; scratch "lookup_dir"): built by the
+    // first key-path lookup after a sort, dropped wherever sorted / keys_valid / heads_valid are reset
+    bool lookup_dir_valid = false;
+    int lookup_dir_bits = 0;   // D: the directory indexes the top D key bits
+    // gk_lookup's pinned host staging: two slots (queries, first, count of one chunk each), so the
+    // host fills one while the copy engine reads the other; lookup_ev[s]: slot s's results landed
+    uint8_t *lookup_pin = nullptr;
+    uint64_t lookup_pin_cap = 0;
+    hipEvent_t lookup_ev[2] = {nullptr, nullptr};
+
     // named, grow-only scratch buffers (MSD sort tables etc.)
     std::map<std::string, std::pair<void *, uint64_t>> scratch;
 

@@ -57,6 +57,7 @@ EXPORTED = (
     "gk_shard_histogram", "gk_shard_sort_range", "gk_shard_class_b", "gk_shard_class_b_copy",
     "gk_shard_sort_range_b", "gk_rank_mode", "gk_reference_random_bases",
     "gk_copy_sequence", "gk_sort_hint", "gk_resident_packed", "gk_set_option",
+    "gk_lookup", "gk_copy_strand_range",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
@@ -151,6 +152,8 @@ _SIGS = {
     "gk_copy_sequence": ([_P, _U8P, ctypes.c_uint64], ctypes.c_int),
     "gk_resident_packed": ([_P, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "gk_set_option": ([ctypes.c_char_p, ctypes.c_char_p], ctypes.c_int),
+    "gk_lookup": ([_P, _U8P, ctypes.c_uint64, ctypes.c_uint32, _U64P, _U32P], ctypes.c_int),
+    "gk_copy_strand_range": ([_P, ctypes.c_uint64, _U8P, ctypes.c_uint64], ctypes.c_int),
 }
 
 
@@ -276,6 +279,56 @@ options = _Options()
 
 def _ptr(arr: np.ndarray, ctype):
     return arr.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+QUERY_ALPHABET = b"ABCDGHKMNRSTVWY"  # the sba alphabet without '$' (gk_lookup's query bytes)
+_QUERY_OK = np.zeros(256, dtype=bool)
+_QUERY_OK[np.frombuffer(QUERY_ALPHABET, dtype=np.uint8)] = True
+
+
+def pack_queries(kmers, kmer_len: int = None) -> np.ndarray:
+    """The query batch of gk_lookup: a C-contiguous uint8 array [m, q] of ASCII bytes.  Host only.
+
+    ``kmers``: one ``str`` / ``bytes`` (m = 1), a sequence of them (all of one length), or a 2-D uint8
+    array.  ValueError: ragged lengths, an empty k-mer, a character outside ABCDGHKMNRSTVWY (upper
+    case; the message names the query's index and the character), or ``kmer_len`` given and different
+    from the k-mers' length."""
+    if isinstance(kmers, np.ndarray):
+        if kmers.ndim != 2 or kmers.dtype != np.uint8:
+            raise ValueError(f"a query array must be 2-D uint8 (ndim = {kmers.ndim}, dtype = {kmers.dtype})")
+        arr = np.ascontiguousarray(kmers)
+        if arr.shape[0] > 0 and arr.shape[1] == 0:
+            raise ValueError("k-mer 0 is empty")
+    else:
+        if isinstance(kmers, (str, bytes, bytearray)):
+            kmers = [kmers]
+        rows = []
+        for i, k in enumerate(kmers):
+            if isinstance(k, str):
+                try:
+                    k = k.encode("ascii")
+                except UnicodeEncodeError:
+                    bad = next(ch for ch in k if ord(ch) > 127)
+                    raise ValueError(f"k-mer {i} holds the character {bad!r}, outside the alphabet "
+                                     f"{QUERY_ALPHABET.decode()}") from None
+            elif not isinstance(k, (bytes, bytearray)):
+                raise ValueError(f"k-mer {i} is neither str nor bytes ({type(k).__name__})")
+            if len(k) == 0:
+                raise ValueError(f"k-mer {i} is empty")
+            if rows and len(k) != len(rows[0]):
+                raise ValueError(f"k-mers differ in length: k-mer {i} has {len(k)} characters, k-mer 0 has "
+                                 f"{len(rows[0])}")
+            rows.append(bytes(k))
+        q = len(rows[0]) if rows else (int(kmer_len) if kmer_len else 1)
+        arr = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), q)
+    if kmer_len is not None and arr.shape[0] > 0 and arr.shape[1] != kmer_len:
+        raise ValueError(f"the k-mers have {arr.shape[1]} characters, kmer_len is {kmer_len}")
+    ok = _QUERY_OK[arr]
+    if not ok.all():
+        i, j = np.argwhere(~ok)[0]
+        raise ValueError(f"k-mer {int(i)} holds the character {chr(int(arr[i, j]))!r}, outside the alphabet "
+                         f"{QUERY_ALPHABET.decode()}")
+    return arr
 
 
 def device_count() -> int:
@@ -461,6 +514,26 @@ class Engine:
             self._check(self.lib.gk_locate(self.ctx, _ptr(nums, ctypes.c_uint64), m, _ptr(sba_idx, ctypes.c_uint32),
                                            _ptr(seg, ctypes.c_uint32)))
         return sba_idx, seg
+
+    def lookup(self, queries: np.ndarray):
+        """(first uint64[m], count uint32[m]) of a pack_queries batch [m, q] in the sorted order
+        (gk_lookup): the matches of query j are the sorted positions [first[j], first[j] + count[j])."""
+        q = np.ascontiguousarray(queries, dtype=np.uint8)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be a 2-D uint8 array (ndim = {q.ndim})")
+        m, qlen = q.shape
+        first = np.empty(m, dtype=np.uint64)
+        count = np.empty(m, dtype=np.uint32)
+        if m:
+            self._check(self.lib.gk_lookup(self.ctx, _ptr(q, ctypes.c_uint8), m, qlen, _ptr(first, ctypes.c_uint64),
+                                           _ptr(count, ctypes.c_uint32)))
+        return first, count
+
+    def strand_range(self, offset: int, count: int) -> np.ndarray:
+        """copy_strands for the sorted positions [offset, offset + count) (gk_copy_strand_range)."""
+        out = np.empty(count, dtype=np.uint8)
+        self._check(self.lib.gk_copy_strand_range(self.ctx, int(offset), _ptr(out, ctypes.c_uint8), int(count)))
+        return out
 
     # ---- multi-GPU shards (genome_kmers.distributed) ------------------------------------------
     def shard_bucket_bits(self) -> int:

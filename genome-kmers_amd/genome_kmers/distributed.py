@@ -321,3 +321,22 @@ class KeyRangeKmerSort:
                                                             canonical=self.canonical)
         self.engine.materialize_keys()  # sorted keys + unique starts and counts stay in HBM
         return self.engine.unique_count_only()
+
+
+def lookup_counts(engine, queries: np.ndarray, group=None, torch_device=None) -> np.ndarray:
+    """Global multiplicity of each query k-mer over the ranks' sorted shards (int64[m], the same on
+    every rank): each rank looks the batch up in its own k-mers (``Engine.lookup``, gk_lookup) and
+    the counts are summed with one ``all_reduce``.  Key-range shards (and the all-to-all's bucket
+    ranges) partition the k-mers -- every k-mer is owned by exactly one rank -- so the sum is the
+    k-mer's count in the whole genome.  ``first`` stays local: it refers to the rank's own order.
+    ``torch_device``: where the reduced tensor lives (the CPU by default, for gloo; the rank's GPU
+    under RCCL)."""
+    import torch
+    import torch.distributed as dist
+
+    _, count = engine.lookup(queries)
+    t = torch.from_numpy(count.astype(np.int64))
+    if torch_device is not None:
+        t = t.to(torch_device)
+    dist.all_reduce(t, group=group)
+    return t.cpu().numpy()

@@ -611,24 +611,30 @@ class Kmers:
             return
         yield from self._full_info(nums, yielded, totals, kmer_len, one_based_seq_index)
 
-    def _full_info(self, nums, yielded, totals, kmer_len, one_based):
-        """get_kmer_info (kmers.py:1180-1264) for every yielded k-mer at once: the starts and their
-        segments come from the device (gk_locate), the rest is vectorised here; a k-mer whose
-        kmer_len runs past its segment raises at its turn, as the reference's generator does."""
+    def _locate_records(self, nums, one_based):
+        """Start, record and position in the record of each kmer_num: the starts and their segments
+        come from the device (gk_locate), the record arithmetic of get_kmer_info (kmers.py:1180-1264)
+        is vectorised here.  Returns (sba_strand, sba, names, seg, start, segment end, seq_idx)."""
         sc = self.seq_coll
         sba_strand = sc._get_sba_strand_to_use(sc.strands_loaded())
         sba, seg_starts, names = sc._strand_arrays(sba_strand)
-        strand_char = "+" if sba_strand == "forward" else "-"
         sba_idx, seg = self._engine.locate(nums)
         starts64 = seg_starts.astype(np.int64)
         b = starts64[seg]
         e = np.where(seg == len(seg_starts) - 1, len(sba) - 1, starts64[np.minimum(seg + 1, len(seg_starts) - 1)] - 2)
         s64 = sba_idx.astype(np.int64)
         seq_idx = (s64 - b if sba_strand == "forward" else e - s64) + (1 if one_based else 0)
+        return sba_strand, sba, tuple(names), seg, s64, e, seq_idx
+
+    def _full_info(self, nums, yielded, totals, kmer_len, one_based):
+        """get_kmer_info (kmers.py:1180-1264) for every yielded k-mer at once (_locate_records); a
+        k-mer whose kmer_len runs past its segment raises at its turn, as the reference's generator
+        does."""
+        sba_strand, sba, names, seg, s64, e, seq_idx = self._locate_records(nums, one_based)
+        strand_char = "+" if sba_strand == "forward" else "-"
         klen = (e - s64 + 1) if kmer_len is None else np.full(len(s64), kmer_len, dtype=np.int64)
         bad = (s64 > e) | ((s64 + klen - 1) > e)
         first_bad = int(np.argmax(bad)) if bad.any() else len(s64)
-        names = tuple(names)
         num_l, y_l, t_l, seg_l, seq_l, k_l = (nums.tolist(), yielded.tolist(), totals.tolist(), seg.tolist(),
                                               seq_idx.tolist(), klen.tolist())
         for i in range(first_bad):
@@ -695,6 +701,59 @@ class Kmers:
             raise AssertionError("The kmers must be sorted when calling get_unique_kmers")
         self._sync_device()
         return self._engine.unique_counts()
+
+    # ---- lookup (no reference counterpart: the reference offers no search) ---------------------
+    def find(self, kmers):
+        """Where the given k-mers sit in the sorted order, searched on the GPU (gk_lookup).
+
+        ``kmers``: one ``str`` / ``bytes``, a sequence of them (one length q), or a 2-D uint8 array
+        (_native.pack_queries).  Returns ``(first, count)``: sorted positions
+        ``[first, first + count)`` hold the k-mers whose first q bases equal the query under the
+        reference's comparison (kmers.py:306-397); ``first`` is the insertion point of an absent
+        query.  Arrays (uint64, uint32), or two ints for a single ``str`` / ``bytes``.  q may be
+        shorter than max_kmer_len (a prefix range); after sort(canonical=True) only
+        q == max_kmer_len, and a query and its reverse complement give the same range."""
+        self._check_forward()
+        if not self._is_sorted:
+            raise AssertionError("The kmers must be sorted when calling find")
+        single = isinstance(kmers, (str, bytes, bytearray))
+        q = _native.pack_queries(kmers)
+        if q.shape[0]:
+            qlen = q.shape[1]
+            if self.max_kmer_len is not None and qlen > self.max_kmer_len:
+                raise ValueError(f"the k-mers have {qlen} characters, more than max_kmer_len ({self.max_kmer_len})")
+            self._check_canonical_len(qlen)
+        self._sync_device()
+        first, count = self._engine.lookup(q)
+        if single:
+            return int(first[0]), int(count[0])
+        return first, count
+
+    def count(self, kmer) -> int:
+        """Number of occurrences of one k-mer (find)."""
+        return int(self.find(kmer)[1])
+
+    def __contains__(self, kmer) -> bool:
+        return self.count(kmer) > 0
+
+    def get_kmer_locations(self, kmer, one_based_seq_index: bool = False) -> list:
+        """[(strand, record_name, seq_idx)] of every occurrence of one k-mer, in sorted (ascending
+        start) order: the range from find, the positions from the device (gk_locate).  After
+        sort(canonical=True) the strand is "-" where the occurrence is the query's canonical form
+        read from the reverse strand (get_canonical_strands of the range), else "+"."""
+        if not isinstance(kmer, (str, bytes, bytearray)):
+            raise ValueError("get_kmer_locations takes one k-mer (str or bytes)")
+        first, count = self.find(kmer)
+        if count == 0:
+            return []
+        nums = np.arange(first, first + count, dtype=np.uint64)
+        sba_strand, _, names, seg, _, _, seq_idx = self._locate_records(nums, one_based_seq_index)
+        strand_char = "+" if sba_strand == "forward" else "-"
+        if self._canonical:
+            strands = ["-" if r else "+" for r in self._engine.strand_range(first, count).tolist()]
+        else:
+            strands = [strand_char] * count
+        return [(st, names[sg], sq) for st, sg, sq in zip(strands, seg.tolist(), seq_idx.tolist())]
 
     def get_encoded_kmers(self) -> np.ndarray:
         """Encoded keys of the sorted k-mers, one row per k-mer."""

@@ -171,6 +171,8 @@ int gk_copy_keys(gk_ctx *ctx, uint64_t *dst, uint64_t n_words);
 /* after a GK_SORT_CANONICAL sort: dst[i] = 1 if the reverse complement of sorted k-mer i is its
  * canonical form (strictly smaller than the k-mer), else 0 (the k-mer itself, or a palindrome) */
 int gk_copy_strands(gk_ctx *ctx, uint8_t *dst, uint64_t n);
+/* the same for the sorted positions [offset, offset + count) only (the hits of a gk_lookup range) */
+int gk_copy_strand_range(gk_ctx *ctx, uint64_t offset, uint8_t *dst, uint64_t count);
 
 /* ---- groups ---------------------------------------------------------------------------------- */
 /* mask for GK_FILTER_MASK: one byte per position of the current start-index order */
@@ -295,6 +297,22 @@ int gk_shard_sort_range_b(gk_ctx *ctx, uint32_t k, uint32_t flags, uint32_t digi
  * (bisect_right over the segment starts, sequence_collection.py:76-97), computed on the device
  * against the resident starts -- the host never needs the whole start array. */
 int gk_locate(gk_ctx *ctx, const uint64_t *kmer_nums, uint64_t m, uint32_t *sba_idx, uint32_t *seg);
+
+/* Batch k-mer lookup in the sorted order (no reference routine: the reference offers no search; the
+ * comparison is its compare_sba_kmers_lexicographically, kmers.py:306-397).  queries: m x qlen ASCII
+ * bytes, row-major, host memory, letters of the sba alphabet without '$'.  Sorted position i matches
+ * query j when compare(sba, query_j, starts[i], 0, max_kmer_len=qlen) == 0: all qlen bytes at
+ * starts[i] equal the query's and none is '$' or past the end (a k-mer that meets its contig's end
+ * first compares less).  first[j] = the number of sorted k-mers that compare less than query j (its
+ * insertion point when it is absent), count[j] = the number that match: the matches are the sorted
+ * positions [first[j], first[j] + count[j]).  1 <= qlen <= the sort length K (a prefix range for
+ * qlen < K; any qlen after a sort with max_kmer_len None).  After GK_SORT_CANONICAL only qlen == K,
+ * and the query stands for min(query, reverse complement): a query and its reverse complement give the
+ * same range.  After a shard sort the answers refer to the rank's own k-mers.  Synchronises the stream.
+ * GK_E_STATE: no sequence, or not sorted; GK_E_ARG: qlen == 0, qlen > K, canonical with qlen != K,
+ * null arrays; GK_E_ALPHABET: a query byte outside the alphabet (checked before any launch; the
+ * message names the query and the byte).  m == 0 returns GK_OK and touches nothing. */
+int gk_lookup(gk_ctx *ctx, const uint8_t *queries, uint64_t m, uint32_t qlen, uint64_t *first, uint32_t *count);
 
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
