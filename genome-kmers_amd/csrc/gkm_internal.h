@@ -197,6 +197,10 @@ struct gk_ctx {
     std::vector<gkm::Timer> timers;
     std::vector<hipEvent_t> ev_pool;  // timing events, created when profiling is switched on and
     size_t ev_used = 0;               // reused (no hipEventCreate inside a timed step)
+
+    // resident workgroups per CU of the sort's persistent-grid kernels, by (kernel pointer, threads
+    // per workgroup): asked of the runtime once per context (gkm_msd.hip resident_per_cu)
+    std::map<std::pair<const void *, int>, int> occupancy;
 };
 
 // ---------------------------------------------------------------------------------------------

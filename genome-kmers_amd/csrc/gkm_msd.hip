@@ -52,7 +52,7 @@ constexpr int kBlockMax = kBT2 * kBI;   // 8192: larger buckets take another glo
 // bucket), 5 = 1024 threads x 8 keys (<= 8192: the buckets an 11-bit L0 + one level leave at C3)
 constexpr int kLocal = 6;
 constexpr int kTiny = 8;
-constexpr int kSmall = 24;
+constexpr int kSmall = 24;                  // sub-buckets <= this: rank-by-count
 // waves per SIMD the wave-local kernels' registers are capped for (msd_wave_kernel<I, W, .>); the
 // LDS (7.2 KB per wave at I = 8) admits 5 per SIMD
 #ifndef GKM_WAVE_OCC8
@@ -72,7 +72,7 @@ constexpr int kSmallLate = 96;
 // The local rounds write back the keys of a bucket only when some of its elements are re-listed
 // (rare): the sort's product is the start order (+ group heads), and keys are re-encoded from the
 // sorted starts when an API call needs them (gk_ctx::keys_stale).
-constexpr int kMaxLevels = 16;              // sub-buckets <= this: rank-by-count
+constexpr int kMaxLevels = 16;              // global levels with a digit width of their own (wsched)
 
 __constant__ uint8_t c_code4_msd[256];
 static bool g_msd_tables = false;
@@ -2640,7 +2640,11 @@ __global__ __launch_bounds__(256) void tie_encode_kernel(const uint8_t *__restri
 // ---------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------
-static int grid_n(uint64_t n) { return (int)std::max<uint64_t>((n + 255) / 256, 1); }
+// blocks of 256 threads over n items, two clamps: at least one block, as many as n needs (lists of
+// buckets, one thread each: an empty list still launches); or at most 65,536 blocks, none for
+// n = 0 (grid-stride kernels over elements)
+static int grid256_min1(uint64_t n) { return (int)std::max<uint64_t>((n + 255) / 256, 1); }
+static unsigned grid256_cap64k(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
 
 hipError_t scan_u32_exclusive_pub(gk_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *total);
 hipError_t scan_u32_exclusive_pair(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
@@ -2679,6 +2683,20 @@ static unsigned cu_count(gk_ctx *c) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 8) cus = 256;
     return (unsigned)(cus / 8 * 8);
 }
+
+// resident workgroups per CU (>= 1) of kernel `fn` at `threads` per workgroup: what sizes a
+// persistent grid.  Asked of the runtime once per context, kernel and block size, so no launch pays
+// for the query again; a query that fails answers 1 and is asked again next time
+static unsigned resident_per_cu(gk_ctx *c, const void *fn, int threads) {
+    auto it = c->occupancy.find({fn, threads});
+    if (it != c->occupancy.end()) return (unsigned)it->second;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1)
+        return 1;  // (not cached: the next launch asks again)
+    c->occupancy[{fn, threads}] = per_cu;
+    return (unsigned)per_cu;
+}
+
 
 // tuning only (A/B runs): GKM_NO_COMPACT=1 keeps 64-bit keys in every level's output
 static bool no_compact() { return opt("GKM_NO_COMPACT") != nullptr; }  // (read per level: tests flip it)
@@ -2722,8 +2740,9 @@ static const char *kPassNamesC[] = {"msd_pass_l0c", "msd_pass_l1c", "msd_pass_l2
                                     "msd_pass_l4c", "msd_pass_l5c", "msd_pass_l6c", "msd_pass_l7c"};  // compact
 
 // One MSD sort of one-word keys into keys[0] / vals[0] (+ group heads).  The first partition
-// comes from the sequence (run_l0) or from received buckets (first_level_from_pieces); the rest
-// -- global levels while buckets exceed kBlockMax, local rounds, done copies -- is common.
+// comes from the sequence (l0_count, l0_start) or from received buckets (first_level_from_pieces);
+// the rest -- global levels while buckets exceed kBlockMax, local rounds, done copies, later phases
+// (run_from) -- is common.  An entry point sets up with begin().
 struct MsdDriver {
     gk_ctx *c;
     KeySpec ks;
@@ -2743,18 +2762,24 @@ struct MsdDriver {
     int width(int level) const { return wsched[std::min(level, kMaxLevels - 1)]; }
     uint8_t *heads = nullptr;
     uint8_t *nd = nullptr;  // next-level digit per element of the last pass's output
-    // compact level (see classify_kernel): the last pass wrote (low key bits, start) pairs and the
-    // next digit instead of keys and starts
-    bool compact_now = false;
+    // The element format of the current buffer, i.e. of what the next level (or the classify behind
+    // the last one) reads; a level's output format is chosen by level_format, what reads what by reads():
+    //   KeyStart       64-bit keys and starts; the next level counts its digits from the keys
+    //   KeyStartDigit  the same plus the next level's digit byte per element in nd
+    //   Pairs          packed pairs (MODE 5): 10-byte (key bits below the sorted ones, start) + the
+    //                  digit byte instead of 12-byte (key, start) + digit, written by the level before
+    //                  a compact one, which reads them (IN79)
+    //   Compact        (low key bits, start) + the next digit instead of keys and starts (see
+    //                  classify_kernel): the local kernels rebuild the keys; the rare large
+    //                  sub-buckets get theirs back at once (expand_big), so a next level reads them as
+    //                  KeyStartDigit
+    //   PackedL0       the packed L0's output (P88, msd0_pipe_kernel): (digit byte, packed pair) in
+    //                  nd_l0 / lo16_l0 / keys
+    enum class Fmt { KeyStart, KeyStartDigit, Pairs, Compact, PackedL0 };
+    Fmt cur_fmt = Fmt::KeyStart;
     int compact_hi = 0;
-    bool nd_ready = false, nd_next = true;
-    // packed-pair levels (MODE 5): the level before a compact one writes 10-byte (key bits below
-    // the sorted ones, start) pairs + the digit byte instead of 12-byte (key, start) + digit; the
-    // compact level reads them (IN79).  allow_c79: msd_sort's own levels
-    bool allow_c79 = false, c79_in = false, c79_out = false;
-    // the packed L0 (P88, msd0_pipe_kernel): its output is (digit byte, packed pair) in nd_l0 /
-    // lo16_l0 / keys; p88_in: the next level reads it (p88_wanted: msd_sort's decision)
-    bool p88 = false, p88_in = false, pieces_level = false;
+    bool allow_c79 = false;  // packed-pair levels allowed (begin)
+    bool p88 = false;        // the L0 writes PackedL0 (p88_wanted: l0_start's decision)
     int p88_shi = 0;
     uint16_t *lo16_l0 = nullptr;
     uint8_t *nd_l0 = nullptr;
@@ -2769,8 +2794,11 @@ struct MsdDriver {
     // final keys: the finishing kernels also write every key to keys[0], so a one-word sort ends
     // with sorted keys + starts + heads in HBM (no re-encode by gather afterwards)
     int wkeys = 0;
-    const uint64_t *pk_code = nullptr;  // packed sequence for the L0 passes (ACGT, 2-bit keys)
-    const uint32_t *pk_dol = nullptr;
+    // the L0 passes' arguments (l0_count fills them in; pk_code / pk_dol, the packed sequence, are set
+    // beforehand by use_resident_pack) and tiles; key-range shards: the ownership digit range
+    // [own_lo, own_lo + own_span) is kept
+    L0Args l0a{};
+    uint64_t l0_tiles = 0;
 
     MsdDriver(gk_ctx *c_, const KeySpec &ks_) : c(c_), ks(ks_), B(ks_.total_bits) {
         cus = cu_count(c);
@@ -2817,6 +2845,14 @@ struct MsdDriver {
                       g ? nullptr : loc_pref[3], g ? nullptr : loc_pref[4], g ? nullptr : loc_pref[5]}};
     }
 
+    // room for `extra` more entries of the done list behind the ndone it holds
+    int grow_done(uint64_t extra) {
+        GK_TRY_HIP(c, grow_keep(c, "dn_start", ndone + extra, ndone, &dn_start));
+        GK_TRY_HIP(c, grow_keep(c, "dn_len", ndone + extra, ndone, &dn_len));
+        GK_TRY_HIP(c, grow_keep(c, "dn_par", ndone + extra, ndone, &dn_par));
+        return GK_OK;
+    }
+
     int init(uint64_t n_) {
         n = n_;
         GK_TRY_HIP(c, msd_tables());
@@ -2833,13 +2869,44 @@ struct MsdDriver {
         GK_TRY_HIP(c, scratch(c, "big_len1", max_big, &big_len[1]));
         GK_TRY_HIP(c, scratch(c, "big_pref0", max_big, &big_pref[0]));
         GK_TRY_HIP(c, scratch(c, "big_pref1", max_big, &big_pref[1]));
-        GK_TRY_HIP(c, grow_keep(c, "dn_start", 1024, 0, &dn_start));
-        GK_TRY_HIP(c, grow_keep(c, "dn_len", 1024, 0, &dn_len));
-        GK_TRY_HIP(c, grow_keep(c, "dn_par", 1024, 0, &dn_par));
+        if (int rc = grow_done(1024)) return rc;  // (ndone = 0: nothing kept)
         for (int k = 0; k < kLocal; ++k) GK_TRY_HIP(c, grow_keep(c, kLocName[k][0], 1024, 0, &loc[k][0]));
         for (int k = 0; k < kLocal; ++k) GK_TRY_HIP(c, grow_keep(c, kLocPrefName[k], 1024, 0, &loc_pref[k]));
         GK_TRY_HIP(c, scratch(c, "msd_heads", n + 64, &heads));
         return GK_OK;
+    }
+
+    // Keys of more than 64 bits are sorted in phases of one word (64 / bits symbols): phase 0 sorts
+    // every k-mer by its first word, each later phase the groups of equal earlier words by the next
+    int symbols_per_word() const { return 64 / ks.bits; }
+    int phases() const { return (ks.symbols + symbols_per_word() - 1) / symbols_per_word(); }
+
+    // The set-up of a sort entry point (all but msd_sort_groups, which sorts inside another sort's
+    // product and neither writes final keys for the context nor takes packed-pair levels):
+    //   B          the bits of the first key word (key_bits: keys that are not made of symbols)
+    //   wkeys      a one-word sort ends with its keys final in keys[0] (c->msd_keys_final) -- but the
+    //              ACGT-only class of a mixed sba only where the split sort asks for them
+    //   allow_c79  packed-pair levels where the bits fit
+    // then the total timer, and the lists for n elements (kInitLater: n is not known yet)
+    static constexpr uint64_t kInitLater = ~0ull;
+    int begin(uint64_t n_, int key_bits = 0) {
+        B = key_bits ? key_bits : ks.bits * std::min(ks.symbols, symbols_per_word());
+        wkeys = (phases() == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;
+        c->msd_keys_final = wkeys != 0;
+        allow_c79 = true;
+        timer_begin(c, "msd_total", &total_slot);
+        return n_ != kInitLater ? init(n_) : GK_OK;
+    }
+
+    // The L0 passes read the packed copy the transfer left beside the sba (gkm_xfer.hip: 0.37 B per
+    // position instead of packing the bytes in every tile) where its stops are the k-mers' stops:
+    // 2-bit keys, and the non-ACGT bytes are '$' alone (an ACGT sba) or all end the k-mers (the
+    // ACGT-only class A of a mixed one).  Returns whether it is used.
+    bool use_resident_pack() {
+        if (!(c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only))) return false;
+        l0a.pk_code = c->res_code;
+        l0a.pk_dol = c->res_dol;
+        return true;
     }
 
     // the list counters and sums: one copy into pinned host memory
@@ -2888,6 +2955,29 @@ struct MsdDriver {
         return GK_OK;
     }
 
+    // a persistent grid: the workgroups of `fn` that are resident at once, at most one per item of work
+    unsigned resident_grid(const void *fn, int threads, uint64_t work) {
+        return (unsigned)std::min<uint64_t>(work, (uint64_t)cus * resident_per_cu(c, fn, threads));
+    }
+
+    // a key-range rank's compacting L0 over the packed copy (l0_dispatch_c, GKM_OWN_L0_COMPACT=1):
+    // count, or partition into packed (pk) or plain output
+    template <int R>
+    void own_launch(bool count, bool pk, const L0Args &a, Dig d0, const OwnTest &ot, unsigned nt0, uint64_t *kout,
+                    uint32_t *vout, uint32_t nt, const NextDigits &ndg) {
+        if (count)
+            hipLaunchKernelGGL(own_count_kernel<R>, dim3(resident_grid((const void *)own_count_kernel<R>, kOwnT, nt0)),
+                               dim3(kOwnT), 0, c->stream, a, d0, ot, tile_hist, nt0);
+        else if (pk)
+            hipLaunchKernelGGL((own_part_kernel<R, true>),
+                               dim3(resident_grid((const void *)own_part_kernel<R, true>, kOwnT, nt0)), dim3(kOwnT), 0,
+                               c->stream, a, d0, ot, tile_hist, kout, vout, nt, ndg);
+        else
+            hipLaunchKernelGGL((own_part_kernel<R, false>),
+                               dim3(resident_grid((const void *)own_part_kernel<R, false>, kOwnT, nt0)), dim3(kOwnT), 0,
+                               c->stream, a, d0, ot, tile_hist, kout, vout, nt, ndg);
+    }
+
     // L0 kernels: count (per-tile digit histograms) or partition; bits x digit width x next digits
     // x canonical
     template <int BITS, int R, bool ND, bool CANON, bool P88 = false, bool OWN = false>
@@ -2896,18 +2986,12 @@ struct MsdDriver {
         // the count pass streams the sequence: 256-thread workgroups, eight per CU, each holding a
         // whole tile of loads in flight (1,024-thread ones, two per CU, kept a quarter as many
         // bytes in flight and measured slower)
-        if (count) {
-            static int per_cu = 0;  // resident workgroups (the grid is persistent)
-            if (!per_cu &&
-                (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                     &per_cu, (const void *)msd0_count_kernel<BITS, kP0T / 4, kP0I * 4, R, CANON>, kP0T / 4, 0) !=
-                     hipSuccess ||
-                 per_cu < 1))
-                per_cu = 1;
+        if (count)
             hipLaunchKernelGGL((msd0_count_kernel<BITS, kP0T / 4, kP0I * 4, R, CANON>),
-                               dim3(std::min<unsigned>(nt0, cus * per_cu)), dim3(kP0T / 4), 0, c->stream, a, d0,
-                               tile_hist, nt0);
-        } else
+                               dim3(resident_grid((const void *)msd0_count_kernel<BITS, kP0T / 4, kP0I * 4, R, CANON>,
+                                                  kP0T / 4, nt0)),
+                               dim3(kP0T / 4), 0, c->stream, a, d0, tile_hist, nt0);
+        else
             hipLaunchKernelGGL((msd0_pipe_kernel<BITS, kP0T, kP0I, R, ND, CANON, P88, OWN>), dim3(pgrid), dim3(kP0T),
                                0, c->stream, a, d0, tile_hist, kout, vout, nt, sink, ndg);
     }
@@ -2916,18 +3000,12 @@ struct MsdDriver {
     void l0_dispatch_c(bool count, int w0, bool nd_, const L0Args &a, Dig d0, unsigned nt0, uint64_t *kout,
                        uint32_t *vout, uint32_t nt, uint64_t sink, const NextDigits &ndg) {
         if (ks.bits == 2 && !CANON && w0 == kWideL0) {  // enable_wide_l0: forward 2-bit one-word sorts
-            if (count) {
-                static int per_cu = 0;
-                if (!per_cu &&
-                    (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         &per_cu, (const void *)msd0_count_kernel<2, 256, kWT * kWI / 256, kWideL0, false>, 256,
-                         0) != hipSuccess ||
-                     per_cu < 1))
-                    per_cu = 1;
+            if (count)
                 hipLaunchKernelGGL((msd0_count_kernel<2, 256, kWT * kWI / 256, kWideL0, false>),
-                                   dim3(std::min<unsigned>(nt0, cus * per_cu)), dim3(256), 0, c->stream, a, d0,
-                                   tile_hist, nt0);
-            } else if (nd_)
+                                   dim3(resident_grid(
+                                       (const void *)msd0_count_kernel<2, 256, kWT * kWI / 256, kWideL0, false>, 256, nt0)),
+                                   dim3(256), 0, c->stream, a, d0, tile_hist, nt0);
+            else if (nd_)
                 hipLaunchKernelGGL((msd0_wide_kernel<kWT, kWI, kWideL0, true>), dim3(pgrid), dim3(kWT), 0, c->stream,
                                    a, d0, tile_hist, kout, vout, nt, sink, ndg);
             else
@@ -2945,27 +3023,8 @@ struct MsdDriver {
             const int sh = 32 - a.own_bits;
             const OwnTest ot{(uint32_t)((uint64_t)a.own_lo << sh),
                              (uint32_t)(((uint64_t)std::min<uint64_t>(a.own_span, 1ull << a.own_bits) << sh) - 1)};
-            auto grid = [&](const void *k) {
-                int per_cu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kOwnT, 0) != hipSuccess || per_cu < 1)
-                    per_cu = 1;
-                return dim3(std::min<unsigned>(nt0, cus * (unsigned)per_cu));
-            };
-#define GK_OWN(R_)                                                                                             \
-    do {                                                                                                       \
-        if (count)                                                                                             \
-            hipLaunchKernelGGL(own_count_kernel<R_>, grid((const void *)own_count_kernel<R_>), dim3(kOwnT), 0,   \
-                               c->stream, a, d0, ot, tile_hist, nt0);                                         \
-        else if (pk)                                                                                           \
-            hipLaunchKernelGGL((own_part_kernel<R_, true>), grid((const void *)own_part_kernel<R_, true>),       \
-                               dim3(kOwnT), 0, c->stream, a, d0, ot, tile_hist, kout, vout, nt, ndg);         \
-        else                                                                                                   \
-            hipLaunchKernelGGL((own_part_kernel<R_, false>), grid((const void *)own_part_kernel<R_, false>),     \
-                               dim3(kOwnT), 0, c->stream, a, d0, ot, tile_hist, kout, vout, nt, ndg);         \
-    } while (0)
-            if (w0 == 7) GK_OWN(7);
-            else GK_OWN(kGR);
-#undef GK_OWN
+            if (w0 == 7) own_launch<7>(count, pk, a, d0, ot, nt0, kout, vout, nt, ndg);
+            else own_launch<kGR>(count, pk, a, d0, ot, nt0, kout, vout, nt, ndg);
             return;
         }
         if (!count && ks.bits == 2 && nd_ && a.own_span != 0xFFFFFFFFu) {  // a key-range rank's fused select
@@ -3002,21 +3061,12 @@ struct MsdDriver {
         else l0_dispatch_c<false>(count, w0, nd_, a, d0, nt0, kout, vout, nt, sink, ndg);
     }
 
-    // L0: encode the k-mers starting in [lo, hi) and partition them by the top kGR key bits into
-    // kout / vout (capacity >= n + 1: element n is the scatter's sink).  seg_base / seg_cnt then
-    // hold the kGRadix buckets.  *count: k-mers found (checked against cap before the scatter).
-    int run_l0(uint64_t lo, uint64_t hi, uint64_t *kout, uint32_t *vout, uint64_t cap, uint64_t *count) {
-        int rc = l0_count(lo, hi, 0, 0xFFFFFFFFu, count);
-        if (rc != GK_OK) return rc;
-        return l0_partition(kout, vout, cap, *count);
-    }
-
-    // key-range shards: the L0 digit range [own_lo, own_lo + own_span) is kept (width(0) bits)
-    L0Args l0a{};
-    uint64_t l0_tiles = 0;
-
+    // L0: the k-mers starting in [lo, hi) encoded and partitioned by their top width(0) key bits, in
+    // two passes over the sequence.  Key-range shards keep only the k-mers whose ownership digit
+    // (the top own_bits key bits) is in [own_lo, own_lo + own_span); all owned: 0, 0xFFFFFFFF.
+    //
     // L0 count pass: per-tile digit histograms of the kept k-mers starting in [lo, hi), their
-    // column scan (seg_base / seg_cnt), *count = k-mers kept
+    // column scan (seg_base / seg_cnt then hold the 2^width(0) buckets), *count = k-mers kept
     int l0_count(uint64_t lo, uint64_t hi, uint32_t own_lo, uint32_t own_span, uint64_t *count, int own_bits = 0) {
         const uint64_t span = hi > lo ? hi - lo : 0;
         const uint64_t tile = wsched[0] == kWideL0 ? (uint64_t)kWT * kWI : (uint64_t)kP0Tile;  // (the wide L0's own)
@@ -3043,8 +3093,8 @@ struct MsdDriver {
         a.own_lo = own_lo;
         a.own_span = own_span;
         if (own_bits) a.own_bits = own_bits;
-        a.pk_code = pk_code;
-        a.pk_dol = pk_dol;
+        a.pk_code = l0a.pk_code;
+        a.pk_dol = l0a.pk_dol;
         l0a = a;
         const int w0 = width(0);
         const Dig d0 = dig_at(B, 0, w0);
@@ -3063,7 +3113,8 @@ struct MsdDriver {
         return GK_OK;
     }
 
-    // L0 partition pass after l0_count (same tiles, same range)
+    // L0 partition pass after l0_count (same tiles, same range) into kout / vout (capacity >=
+    // count + 1: element `count` is the scatter's sink)
     int l0_partition(uint64_t *kout, uint32_t *vout, uint64_t cap, uint64_t count) {
         if (count + 1 > cap) return fail(c, GK_E_ARG, "partition output buffer too small");
         const int w0 = width(0);
@@ -3089,8 +3140,7 @@ struct MsdDriver {
         l0_dispatch(false, w0, with_nd, l0a, d0, (unsigned)l0_tiles, kout, vout, (uint32_t)l0_tiles, count, ndg);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
-        nd_ready = with_nd;
-        p88_in = with_nd && p88;
+        cur_fmt = !with_nd ? Fmt::KeyStart : p88 ? Fmt::PackedL0 : Fmt::KeyStartDigit;
         return GK_OK;
     }
 
@@ -3146,6 +3196,28 @@ struct MsdDriver {
         return GK_OK;
     }
 
+    // The start of a sort from the sequence, behind l0_count (which found the n = `found` k-mers this
+    // sort keeps) and init(found): the L0 partition into the buffer *in, its buckets routed.
+    int l0_start(uint64_t found, int *in) {
+        // the packed L0 output (P88) when the level behind it writes packed pairs
+        p88 = p88_wanted();  // (multi-word keys: phase 0's first word; the tie phases read keys[0] / vals[0])
+        p88_shi = 64 - (B - width(0) - 8);
+        // The L0's output buffer: the one that makes the last global level write buffer 1, so that the
+        // finishing kernels read buffer 1 and write buffer 0 instead of rewriting buffer 0 in place
+        // (levels predicted from the mean bucket size; C3: L0, L1, L2 -> L0 writes buffer 1).  A/B on
+        // one box (C3, 3 pairs): 67.3-68.3 against 67.7-68.8 ms.
+        uint64_t mean = found >> width(0);
+        int lev = 0;
+        for (int l = 1; mean > (uint64_t)kBlockMax && l < kMaxLevels; ++l, ++lev) mean >>= width(l);
+        const int l0b = 1 ^ (lev & 1);
+        *in = l0b;
+        int rc = l0_partition(c->keys[l0b], c->vals[l0b], c->elem_cap + 64, found);
+        if (rc != GK_OK) return rc;
+        rc = classify(1u << width(0), width(0), l0b, 0, nullptr, nullptr, 1, nullptr, width(0));
+        if (rc != GK_OK) return rc;
+        return cur_fmt == Fmt::PackedL0 ? expand_p88_locals(l0b) : GK_OK;  // (skewed genomes: L0 buckets finished locally)
+    }
+
     // one region of the prefetched L0 (L0Prefetch, below): count, column scan and partition of the
     // k-mers starting in [lo, hi) into keys[1] / vals[1] / nd at output indices from lo, then the
     // region's 2^w0 bucket bases and counts into `pieces` -- all on c->stream (the caller points it
@@ -3183,7 +3255,7 @@ struct MsdDriver {
     // after a compact level: the (rare) sub-buckets that go to another global level get their keys
     // back in keys[out], so that level reads keys as usual (the digit bytes stay valid for it)
     int expand_big(int out) {
-        if (!compact_now || nbig == 0) return GK_OK;
+        if (cur_fmt != Fmt::Compact || nbig == 0) return GK_OK;
         hipLaunchKernelGGL(expand_compact_kernel, dim3(nbig, bucket_split(nbig)), dim3(256), 0, c->stream, big_start[cur_big],
                            big_len[cur_big], big_pref[cur_big], compact_hi, B, nd, c->keys[out], c->vals[out]);
         GK_TRY_HIP(c, hipGetLastError());
@@ -3202,9 +3274,7 @@ struct MsdDriver {
             GK_TRY_HIP(c, grow_keep(c, kLocName[k][0], nloc[k] + nsub, nloc[k], &loc[k][0]));
         for (int k = 0; k < kLocal; ++k)
             GK_TRY_HIP(c, grow_keep(c, kLocPrefName[k], nloc[k] + nsub, nloc[k], &loc_pref[k]));
-        GK_TRY_HIP(c, grow_keep(c, "dn_start", ndone + nsub, ndone, &dn_start));
-        GK_TRY_HIP(c, grow_keep(c, "dn_len", ndone + nsub, ndone, &dn_len));
-        GK_TRY_HIP(c, grow_keep(c, "dn_par", ndone + nsub, ndone, &dn_par));
+        if (int rc = grow_done(nsub)) return rc;
         GK_TRY_HIP(c, hipMemsetAsync(ctr + kCtrBig, 0, 4, c->stream));
         GK_TRY_HIP(c, hipMemsetAsync(sums, 0, 8 * kSumN, c->stream));
         timer_begin(c, "msd_classify", &slot);
@@ -3216,7 +3286,8 @@ struct MsdDriver {
         return read ? classify_counts() : GK_OK;
     }
 
-    // the lists classify wrote (and drop_uniform_dev re-routed), to the host
+    // the lists classify wrote (and route_uniform's device-count path re-routed), to the host: only
+    // behind a classify that did not read back itself (loc_elems is added to)
     int classify_counts() {
         int r = read_ctr();
         if (r != GK_OK) return r;
@@ -3230,42 +3301,77 @@ struct MsdDriver {
         return GK_OK;
     }
 
-    // drop_uniform with no read-back of its own, behind a classify that did not read its lists
-    // either (the deep levels of a repeat-rich genome: one host round trip per level instead of
-    // two): the next-level list's count stays on the device; `bound` >= that count sizes the grids
-    // (the blocks past the count return at once).  Ends with classify_counts.
-    int drop_uniform_dev(int out, uint32_t bound) {
-        const uint32_t *nb_dev = ctr + kCtrBig;
-        const unsigned split = bucket_split(bound);
-        if (compact_now)
-            hipLaunchKernelGGL(expand_compact_kernel, dim3(bound, split), dim3(256), 0, c->stream, big_start[cur_big],
+    // Before another global level: the buckets of the next-level list whose keys are all equal go to
+    // the done list, the others to the other next-level list (keys in keys[out]).  Two callers:
+    //   dev_count = false  behind a classify that read its lists: nb = nbig, exact grids, and only
+    //       what this changes is read back (ndone, nbig, big_elems).  NOT classify_counts: that adds
+    //       the local lists' element sums to loc_elems, which the classify's read already did.
+    //   dev_count = true   behind a classify that did not read back (the deep levels of a repeat-rich
+    //       genome: one host round trip per level instead of two): the list's count stays on the
+    //       device, nb >= that count sizes the grids (the blocks past the count return at once), a
+    //       compact level's buckets get their keys back here (the host path's expand_big), and the
+    //       one read-back is the classify's own (classify_counts).
+    int route_uniform(int out, uint32_t nb, bool dev_count) {
+        const uint32_t *nb_dev = dev_count ? ctr + kCtrBig : nullptr;
+        uint32_t *nb_copy = dev_count ? ctr + kCtrNbCopy : nullptr;  // (the flag kernel's copy: kCtrBig is reset)
+        const unsigned split = bucket_split(nb);
+        if (dev_count && cur_fmt == Fmt::Compact)
+            hipLaunchKernelGGL(expand_compact_kernel, dim3(nb, split), dim3(256), 0, c->stream, big_start[cur_big],
                                big_len[cur_big], big_pref[cur_big], compact_hi, B, nd, c->keys[out], c->vals[out],
                                nb_dev);
         uint32_t *mixed;
-        GK_TRY_HIP(c, scratch(c, "uni_mixed", bound, &mixed));
-        GK_TRY_HIP(c, hipMemsetAsync(mixed, 0, 4ull * bound, c->stream));
-        hipLaunchKernelGGL(uniform_flag_kernel, dim3(bound, split), dim3(256), 0, c->stream, big_start[cur_big],
-                           big_len[cur_big], c->keys[out], mixed, nb_dev, ctr + kCtrNbCopy);
-        // (the done list has room: classify grew it by every sub-bucket, and each goes to one list)
+        GK_TRY_HIP(c, scratch(c, "uni_mixed", nb, &mixed));
+        GK_TRY_HIP(c, hipMemsetAsync(mixed, 0, 4ull * nb, c->stream));
+        hipLaunchKernelGGL(uniform_flag_kernel, dim3(nb, split), dim3(256), 0, c->stream, big_start[cur_big],
+                           big_len[cur_big], c->keys[out], mixed, nb_dev, nb_copy);
+        // (dev_count: the done list has room -- the classify grew it by every sub-bucket, and each
+        // goes to one list)
+        if (!dev_count)
+            if (int rc = grow_done(nb)) return rc;
         GK_TRY_HIP(c, hipMemsetAsync(ctr + kCtrBig, 0, 4, c->stream));
         GK_TRY_HIP(c, hipMemsetAsync(sums + kCtrBig, 0, 8, c->stream));
         GK_TRY_HIP(c, hipMemsetAsync(sums + kSumTiles, 0, 16, c->stream));
-        hipLaunchKernelGGL(route_uniform_kernel, dim3(grid_n(bound)), dim3(256), 0, c->stream, big_start[cur_big],
-                           big_len[cur_big], big_pref[cur_big], bound, mixed, lists(0, cur_big ^ 1), out, ctr, sums,
-                           (uint32_t)kPTile, ctiles, ctr + kCtrNbCopy);
+        hipLaunchKernelGGL(route_uniform_kernel, dim3(grid256_min1(nb)), dim3(256), 0, c->stream, big_start[cur_big],
+                           big_len[cur_big], big_pref[cur_big], nb, mixed, lists(0, cur_big ^ 1), out, ctr, sums,
+                           (uint32_t)kPTile, ctiles, nb_copy);
         GK_TRY_HIP(c, hipGetLastError());
         cur_big ^= 1;
-        return classify_counts();
+        if (dev_count) return classify_counts();
+        int r = read_ctr();
+        if (r != GK_OK) return r;
+        ndone = h[kCtrDone];
+        nbig = h[kCtrBig];
+        big_elems = hs[kCtrBig];
+        return GK_OK;
     }
 
+    // route_uniform pays once the next-level buckets hold few elements: after L1 of a random genome
+    // they hold all of them and are never uniform (`elems`: the level's output, or its input where
+    // the decision comes before the classify's read-back)
+    bool few_big_elems(int level, uint64_t elems) const {
+        return level >= 1 && elems * 64 <= std::max<uint64_t>(c->n, 1);
+    }
+
+    // Which input format a level writing `out` reads as it is; any other input goes back to (key,
+    // start) + digit bytes first, by the expand_* launches of whoever holds the buckets (level_pass:
+    // the next-level list; first_level_from_pieces: the pieces).
+    static bool reads(Fmt in, Fmt out) {
+        switch (in) {
+        case Fmt::Pairs: return out == Fmt::Compact;    // (msd_pipe_kernel<..., 4, ., ., IN79>)
+        case Fmt::PackedL0: return out == Fmt::Pairs;   // (msd_pipe_kernel<..., 5, ., ., INP = 2>)
+        default: return true;  // keys and starts (a compact level's large buckets: expand_big made them so)
+        }
+    }
+    bool has_digits() const { return cur_fmt != Fmt::KeyStart; }
+
     // one global partition level (R-bit digits below the top hi bits) over tiles already in
-    // t_start / t_count (T tiles, C chunks, nseg buckets), reading kin / vin, writing keys[out] /
-    // vals[out] and the next level's digit bytes
+    // t_start / t_count (T tiles, C chunks, nseg buckets), reading kin / vin (format cur_fmt), writing
+    // keys[out] / vals[out] in format ofmt
     template <int R>
     void level_launch(int hi, int nw, const uint32_t *t_start, const uint32_t *t_count, uint64_t T,
-                      const uint64_t *kin, const uint32_t *vin, int out, bool count) {
+                      const uint64_t *kin, const uint32_t *vin, int out, bool count, Fmt ofmt) {
         if (count) {
-            if (nd_ready)  // the previous pass wrote this level's digits
+            if (has_digits())  // the previous pass wrote this level's digits
                 hipLaunchKernelGGL(msd_count_nd_kernel<R>, dim3((unsigned)T), dim3(256), 0, c->stream, t_start,
                                    t_count, nd, tile_hist);
             else
@@ -3273,11 +3379,11 @@ struct MsdDriver {
                                    dig_at(B, hi, R), kin, tile_hist);
             return;
         }
-        if (compact_now) {
+        if (ofmt == Fmt::Compact) {
             const int rem = B - hi - R;  // 9..40: key bits below this level's digit
             NextDigits ndg{dig_at(B, hi + R, 8), nd};
             ndg.lowmask = (uint32_t)((1ull << (rem - 8)) - 1);
-            if (c79_in)  // the previous level wrote packed pairs
+            if (cur_fmt == Fmt::Pairs)  // the previous level wrote packed pairs
                 hipLaunchKernelGGL((msd_pipe_kernel<kPT, kPI, R, 4, true, 0, true>), dim3(pgrid), dim3(kPT), 0,
                                    c->stream, t_start, t_count, dig_at(B, hi, R), tile_hist, kin, vin, c->keys[out],
                                    c->vals[out], (uint32_t)T, n, ndg, lo16, c79_shi);
@@ -3287,11 +3393,11 @@ struct MsdDriver {
                                    c->vals[out], (uint32_t)T, n, ndg);
             return;
         }
-        if (c79_out) {  // packed pairs for the compact level behind this one
+        if (ofmt == Fmt::Pairs) {  // packed pairs for the compact level behind this one
             NextDigits ndg{dig_at(B, hi + R, nw), nd};
             ndg.out16 = lo16;
             ndg.pshi = c79_shi;
-            if (p88_in) {  // reading the packed L0's output
+            if (cur_fmt == Fmt::PackedL0) {  // reading the packed L0's output
                 ndg.in8 = nd_l0;
                 hipLaunchKernelGGL((msd_pipe_kernel<kPT, kPI, R, 5, true, 0, 2>), dim3(pgrid), dim3(kPT), 0, c->stream,
                                    t_start, t_count, dig_at(B, hi, R), tile_hist, kin, vin, c->keys[out], c->vals[out],
@@ -3304,7 +3410,7 @@ struct MsdDriver {
             return;
         }
         const NextDigits ndg{dig_at(B, hi + R, nw), nd};
-        if (nd_next)
+        if (ofmt == Fmt::KeyStartDigit)
             hipLaunchKernelGGL((msd_pipe_kernel<kPT, kPI, R, 0, true>), dim3(pgrid), dim3(kPT), 0, c->stream, t_start,
                                t_count, dig_at(B, hi, R), tile_hist, kin, vin, c->keys[out], c->vals[out],
                                (uint32_t)T, n, ndg);
@@ -3315,90 +3421,78 @@ struct MsdDriver {
     }
 
     void level_dispatch(int level, int hi, const uint32_t *t_start, const uint32_t *t_count, uint64_t T,
-                        const uint64_t *kin, const uint32_t *vin, int out, bool count) {
+                        const uint64_t *kin, const uint32_t *vin, int out, bool count, Fmt ofmt) {
         const int w = width(level), nw = width(level + 1);
-        if (w == 8) level_launch<8>(hi, nw, t_start, t_count, T, kin, vin, out, count);
-        else if (w == 7) level_launch<7>(hi, nw, t_start, t_count, T, kin, vin, out, count);
-        else level_launch<6>(hi, nw, t_start, t_count, T, kin, vin, out, count);
+        if (w == 8) level_launch<8>(hi, nw, t_start, t_count, T, kin, vin, out, count, ofmt);
+        else if (w == 7) level_launch<7>(hi, nw, t_start, t_count, T, kin, vin, out, count, ofmt);
+        else level_launch<6>(hi, nw, t_start, t_count, T, kin, vin, out, count, ofmt);
     }
 
-    // the output format of a global level over nseg buckets holding elems elements (level_pass):
-    //   nd_next  the next level's digit bytes are written (its sub-buckets are most likely big);
-    //   compact  (low bits, start) + digit byte, 9 B out, when its sub-buckets will most likely all
+    // the output format of a global level over nseg buckets holding elems elements, reading cur_fmt:
+    //   KeyStartDigit  the next level's digit bytes are written too (its sub-buckets are most likely
+    //                  big); KeyStart otherwise: a next level then counts from the keys;
+    //   Compact  (low bits, start) + digit byte, 9 B out, when its sub-buckets will most likely all
     //            be finished locally and the key bits below the next 8-bit digit fit a u32;
-    //   pairs    packed pairs (10 B + digit byte) when the next level is most likely compact (its
+    //   Pairs    packed pairs (10 B + digit byte) when the next level is most likely compact (its
     //            sub-buckets local, its remaining bits <= 40) and this level's remaining key bits
     //            and the start fit 80 bits (GKM_TEST_PAIRS=1, tests: whenever the bits fit)
-    struct LevelFormat {
-        bool nd_next, compact, pairs;
-    };
-    LevelFormat level_format(int level, int hi, uint64_t elems, uint64_t nseg) const {
-        LevelFormat f{};
-        f.nd_next = nseg == 0 || (elems / nseg >> width(level)) >= (uint64_t)kBlockMax;
+    Fmt level_format(int level, int hi, uint64_t elems, uint64_t nseg) const {
+        const bool digits = nseg == 0 || (elems / nseg >> width(level)) >= (uint64_t)kBlockMax;
         const int rem = B - hi - width(level);
-        f.compact = phase == 0 && !f.nd_next && rem >= 9 && rem <= 40 && width(level + 1) == 8 && !no_compact();
+        if (phase == 0 && !digits && rem >= 9 && rem <= 40 && width(level + 1) == 8 && !no_compact())
+            return Fmt::Compact;
         const uint64_t next_mean = nseg ? (elems / nseg >> width(level)) >> width(level + 1) : 0;
         const int rem2 = rem - width(level + 1);
         const bool force = opt("GKM_TEST_PAIRS") != nullptr;  // (read per level: tests flip it)
-        f.pairs = allow_c79 && !c79_in && phase == 0 && !f.compact && rem >= 33 && rem <= 48 && !no_compact() &&
-                  (force || (f.nd_next && next_mean < (uint64_t)kBlockMax && rem2 >= 9 && rem2 <= 40 &&
-                             width(level + 2) == 8 && width(level + 1) == 8));
-        return f;
+        if (allow_c79 && cur_fmt != Fmt::Pairs && phase == 0 && rem >= 33 && rem <= 48 && !no_compact() &&
+            (force || (digits && next_mean < (uint64_t)kBlockMax && rem2 >= 9 && rem2 <= 40 &&
+                       width(level + 2) == 8 && width(level + 1) == 8)))
+            return Fmt::Pairs;
+        return digits ? Fmt::KeyStartDigit : Fmt::KeyStart;
     }
 
     int level_pass(int level, int hi, const uint32_t *t_start, const uint32_t *t_count, uint64_t T, uint64_t C,
                    const uint32_t *s_cfirst, const uint32_t *s_nchunks, const uint32_t *s_start, uint64_t nseg,
                    const uint64_t *kin, const uint32_t *vin, int out) {
-        timer_begin(c, nd_ready ? "msd_count_nd" : "msd_count", &slot);
+        timer_begin(c, has_digits() ? "msd_count_nd" : "msd_count", &slot);
         timer_units(c, slot, big_elems);
-        level_dispatch(level, hi, t_start, t_count, T, kin, vin, out, true);
+        level_dispatch(level, hi, t_start, t_count, T, kin, vin, out, true, cur_fmt);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
         int rc = scan_offsets(width(level), C, s_cfirst, s_nchunks, s_start, nseg);
         if (rc != GK_OK) return rc;
         GK_TRY_HIP(c, scratch(c, "msd_nd", n + 64, &nd));
-        // the next level's digit bytes, unless this level's sub-buckets will most likely all be
-        // local (mean under kBlockMax); a next level then counts from the keys
-        const LevelFormat lf = level_format(level, hi, big_elems, nseg);
-        nd_next = lf.nd_next;
-        compact_now = lf.compact;
+        const Fmt ofmt = level_format(level, hi, big_elems, nseg);
         compact_hi = hi + width(level);
-        c79_out = lf.pairs;
         const int rem = B - hi - width(level);
-        if (c79_out) {
+        if (ofmt == Fmt::Pairs) {
             c79_shi = 64 - rem;
             GK_TRY_HIP(c, scratch(c, "msd_lo16", n + 64, &lo16));
         }
-        // the packed L0's output in, but no packed pairs out: back to (key, start) first
-        if (p88_in && !c79_out) {
-            if (pieces_level)  // (first_level_from_pieces expands its pieces itself beforehand)
-                return fail(c, GK_E_HIP, "msd: packed L0 pieces reached a level that does not read them");
-            if (int rc = p88_detach()) return rc;
-            hipLaunchKernelGGL(expand_p88_kernel, dim3((unsigned)nseg, bucket_split(nseg)), dim3(256), 0, c->stream,
-                               big_start[cur_big], big_len[cur_big], big_pref[cur_big], hi, B, p88_shi,
-                               const_cast<uint64_t *>(kin), lo16_l0, nd_l0, const_cast<uint32_t *>(vin));
+        if (!reads(cur_fmt, ofmt)) {  // back to (key, start) first; the digit bytes stay
+            if (cur_fmt == Fmt::PackedL0) {
+                if (int rc = p88_detach()) return rc;
+                hipLaunchKernelGGL(expand_p88_kernel, dim3((unsigned)nseg, bucket_split(nseg)), dim3(256), 0,
+                                   c->stream, big_start[cur_big], big_len[cur_big], big_pref[cur_big], hi, B, p88_shi,
+                                   const_cast<uint64_t *>(kin), lo16_l0, nd_l0, const_cast<uint32_t *>(vin));
+            } else {  // Pairs
+                hipLaunchKernelGGL(expand_pair_kernel, dim3((unsigned)nseg, bucket_split(nseg)), dim3(256), 0,
+                                   c->stream, big_start[cur_big], big_len[cur_big], big_pref[cur_big], hi, B, c79_shi,
+                                   const_cast<uint64_t *>(kin), lo16, const_cast<uint32_t *>(vin));
+            }
             GK_TRY_HIP(c, hipGetLastError());
-            p88_in = false;
+            cur_fmt = Fmt::KeyStartDigit;
         }
-        // packed pairs in, but not a compact level after all: back to (key, start) first
-        if (c79_in && !compact_now) {
-            hipLaunchKernelGGL(expand_pair_kernel, dim3((unsigned)nseg, bucket_split(nseg)), dim3(256), 0, c->stream,
-                               big_start[cur_big], big_len[cur_big], big_pref[cur_big], hi, B, c79_shi,
-                               const_cast<uint64_t *>(kin), lo16, const_cast<uint32_t *>(vin));
-            GK_TRY_HIP(c, hipGetLastError());
-            c79_in = false;
-        }
-        timer_begin(c, compact_now ? kPassNamesC[level & 7] : c79_out ? kPassNamesP[level & 7] : kPassNames[level & 7],
+        timer_begin(c, ofmt == Fmt::Compact ? kPassNamesC[level & 7] : ofmt == Fmt::Pairs ? kPassNamesP[level & 7]
+                                                                                          : kPassNames[level & 7],
                     &slot);
         timer_units(c, slot, big_elems);
-        level_dispatch(level, hi, t_start, t_count, T, kin, vin, out, false);
+        level_dispatch(level, hi, t_start, t_count, T, kin, vin, out, false, ofmt);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
-        // a compact or packed-pair level wrote the next 8-bit digit too (the next count must not
-        // read keys: pairs hold them shifted)
-        nd_ready = nd_next || compact_now || c79_out;
-        c79_in = c79_out;  // the next level's input format
-        p88_in = false;
+        // (a compact or packed-pair level wrote the next 8-bit digit too: the next count must not
+        // read keys -- pairs hold them shifted)
+        cur_fmt = ofmt;
         return GK_OK;
     }
 
@@ -3473,7 +3567,10 @@ struct MsdDriver {
         GK_TRY_HIP(c, hipMemcpyAsync(s_pref, spf.data(), 8 * nseg, hipMemcpyHostToDevice, c->stream));
         GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
         big_elems = n;
-        if (p88_in && !level_format(level, hi, n, nseg).pairs) {  // (prefetched packed L0: back to (key, start))
+        // the reads() rule applied here, where the elements are held as pieces and not as a list of
+        // buckets (pieces come as key/start forms or, from the prefetched L0, PackedL0): level_pass
+        // below then chooses the same output format and finds an input it reads
+        if (!reads(cur_fmt, level_format(level, hi, n, nseg))) {
             if (int rd = p88_detach()) return rd;
             uint64_t *pdev;
             GK_TRY_HIP(c, scratch(c, "p88_pieces", 3 * np, &pdev));
@@ -3489,50 +3586,77 @@ struct MsdDriver {
                                const_cast<uint32_t *>(vin));
             GK_TRY_HIP(c, hipGetLastError());
             GK_TRY_HIP(c, hipStreamSynchronize(c->stream));  // (hp is released at return)
-            p88_in = false;
+            cur_fmt = Fmt::KeyStartDigit;
         }
-        pieces_level = true;
         rc = level_pass(level, hi, t_start, t_count, T, C, s_cfirst, s_nchunks, s_st, nseg, kin, vin, 0);
-        pieces_level = false;
         if (rc != GK_OK) return rc;
         cur_big = 0;
         uint64_t before[kLocal];
         for (int k = 0; k < kLocal; ++k) before[k] = nloc[k];
         rc = classify(nseg << width(level), hi + width(level), 0, cur_big, nullptr, nullptr, 1, s_pref, width(level),
-                      compact_now ? 1 : 0);
+                      cur_fmt == Fmt::Compact ? 1 : 0);
         // (as levels(): a packed-pair level's local sub-buckets back to (key, start))
-        if (rc == GK_OK && c79_out) rc = expand_pair_locals(before, 0);
+        if (rc == GK_OK && cur_fmt == Fmt::Pairs) rc = expand_pair_locals(before, 0);
         return rc == GK_OK ? expand_big(0) : rc;
+    }
+
+    unsigned tie_tiles() const { return (unsigned)std::max<uint64_t>((n + kTieTile - 1) / kTieTile, 1); }
+
+    // The groups of >= 2 elements among the n that `flags` marks (a 1 starts a group), as *ng
+    // (start, length) entries in scratch "tie_start" / "tie_len": the groups' firsts and lasts are
+    // counted per tile, scanned, stored, and the lasts turned into lengths.  With no group (*ng = 0)
+    // nothing is allocated or stored: the store pass would write nothing.  *tile_cnt / *tile_off
+    // (optional): two of the pass's per-tile arrays (tie_tiles() + 1 words each), free for reuse.
+    int tie_groups(const uint8_t *flags, uint32_t **g_start, uint32_t **g_len, uint64_t *ng,
+                   uint32_t **tile_cnt = nullptr, uint32_t **tile_off = nullptr) {
+        const unsigned ttiles = tie_tiles();
+        uint32_t *cf, *cl, *of, *ol;
+        GK_TRY_HIP(c, scratch(c, "tie_cnt_f", ttiles + 1, &cf));
+        GK_TRY_HIP(c, scratch(c, "tie_cnt_l", ttiles + 1, &cl));
+        GK_TRY_HIP(c, scratch(c, "tie_off_f", ttiles + 1, &of));
+        GK_TRY_HIP(c, scratch(c, "tie_off_l", ttiles + 1, &ol));
+        if (tile_cnt) *tile_cnt = cf;
+        if (tile_off) *tile_off = of;
+        hipLaunchKernelGGL(tie_bounds_kernel<false>, dim3(ttiles), dim3(256), 0, c->stream, flags, n, cf, cl, nullptr,
+                           nullptr, nullptr, nullptr);
+        GK_TRY_HIP(c, hipGetLastError());
+        uint64_t ng2 = 0;
+        GK_TRY_HIP(c, scan_u32_exclusive_pair(c, cf, of, cl, ol, ttiles, ng, &ng2));
+        if (*ng != ng2) return fail(c, GK_E_HIP, "msd: tie group bounds do not pair up");
+        if (*ng == 0) return GK_OK;
+        GK_TRY_HIP(c, scratch(c, "tie_start", *ng + 64, g_start));
+        GK_TRY_HIP(c, scratch(c, "tie_len", *ng + 64, g_len));
+        hipLaunchKernelGGL(tie_bounds_kernel<true>, dim3(ttiles), dim3(256), 0, c->stream, flags, n, nullptr, nullptr,
+                           of, ol, *g_start, *g_len);
+        GK_TRY_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(tie_run_lengths_kernel, dim3((unsigned)std::min<uint64_t>((*ng + 255) / 256, 8192)),
+                           dim3(256), 0, c->stream, *g_start, *g_len, *ng);
+        GK_TRY_HIP(c, hipGetLastError());
+        return GK_OK;
+    }
+
+    // the tie groups of keys[0] / vals[0], each sorted stably by the B-bit keys, in place: the groups
+    // are the first buckets; global levels from level 1 with no bits sorted, local rounds, done copies
+    int sort_tied(const uint32_t *g_start, const uint32_t *g_len, uint64_t ng) {
+        cur_fmt = Fmt::KeyStart;
+        int rc = classify(ng, 0, 0, cur_big, g_start, g_len, 2);
+        if (rc != GK_OK) return rc;
+        rc = levels(1, 0, 0);
+        if (rc != GK_OK) return rc;
+        return finish();
     }
 
     // Multi-word keys, phase > 0: the head flags of the order so far (buffer 0) mark the groups of
     // equal earlier words; sort each group of >= 2 by the key word of symbols [sym0, sym0 + nsym).
     int next_phase(int sym0, int nsym) {
         uint32_t *g_start, *g_len;
+        uint64_t ng = 0;
         timer_begin(c, "msd_tie_groups", &slot);
-        const unsigned ttiles = (unsigned)std::max<uint64_t>((n + kTieTile - 1) / kTieTile, 1);
-        uint32_t *cf, *cl, *of, *ol;
-        GK_TRY_HIP(c, scratch(c, "tie_cnt_f", ttiles + 1, &cf));
-        GK_TRY_HIP(c, scratch(c, "tie_cnt_l", ttiles + 1, &cl));
-        GK_TRY_HIP(c, scratch(c, "tie_off_f", ttiles + 1, &of));
-        GK_TRY_HIP(c, scratch(c, "tie_off_l", ttiles + 1, &ol));
-        hipLaunchKernelGGL(tie_bounds_kernel<false>, dim3(ttiles), dim3(256), 0, c->stream, heads, n, cf, cl, nullptr,
-                           nullptr, nullptr, nullptr);
-        GK_TRY_HIP(c, hipGetLastError());
-        uint64_t ng = 0, ng2 = 0;
-        GK_TRY_HIP(c, scan_u32_exclusive_pair(c, cf, of, cl, ol, ttiles, &ng, &ng2));
-        GK_TRY_HIP(c, scratch(c, "tie_start", ng + 64, &g_start));
-        GK_TRY_HIP(c, scratch(c, "tie_len", ng2 + 64, &g_len));
-        hipLaunchKernelGGL(tie_bounds_kernel<true>, dim3(ttiles), dim3(256), 0, c->stream, heads, n, nullptr, nullptr,
-                           of, ol, g_start, g_len);
-        GK_TRY_HIP(c, hipGetLastError());
-        if (ng != ng2) return fail(c, GK_E_HIP, "msd: tie group bounds do not pair up");
-        if (ng > 0)
-            hipLaunchKernelGGL(tie_run_lengths_kernel, dim3((unsigned)std::min<uint64_t>((ng + 255) / 256, 8192)),
-                               dim3(256), 0, c->stream, g_start, g_len, ng);
-        GK_TRY_HIP(c, hipGetLastError());
+        uint32_t *cf, *of;  // (per-tile counts and offsets: the member list below reuses them)
+        if (int rc = tie_groups(heads, &g_start, &g_len, &ng, &cf, &of)) return rc;
         timer_end(c, slot);
         if (ng == 0) return GK_OK;
+        const unsigned ttiles = tie_tiles();
         timer_begin(c, "msd_tie_encode", &slot);
         const unsigned grid = (unsigned)std::min<uint64_t>((ng + 3) / 4, (uint64_t)cus * 16);
         bool flat = ng > 4096;
@@ -3545,10 +3669,9 @@ struct MsdDriver {
             flat = tot > (1u << 20);
         }
         if (flat) {  // many groups: the members listed from the head flags, then one thread per member
-            uint32_t *mlist;
             // the list lives in the free key buffer (8 B per element; classify and the levels below
             // reuse it only after the encode has read the list)
-            mlist = reinterpret_cast<uint32_t *>(c->keys[1]);
+            uint32_t *mlist = reinterpret_cast<uint32_t *>(c->keys[1]);
             hipLaunchKernelGGL(tie_members_kernel<false>, dim3(ttiles), dim3(256), 0, c->stream, heads, n, cf, nullptr,
                                nullptr);
             GK_TRY_HIP(c, hipGetLastError());
@@ -3578,13 +3701,7 @@ struct MsdDriver {
         ndone = 0;
         nbig = 0;
         for (int k = 0; k < kLocal; ++k) nloc[k] = loc_elems[k] = 0;
-        nd_ready = false;
-        c79_in = false;
-        int rc = classify(ng, 0, 0, cur_big, g_start, g_len, 2);
-        if (rc != GK_OK) return rc;
-        rc = levels(1, 0, 0);
-        if (rc != GK_OK) return rc;
-        return finish();
+        return sort_tied(g_start, g_len, ng);
     }
 
     // Prefix doubling (gkm_capi.hip sort_doubling): every run of >= 2 elements of keys[0] / vals[0]
@@ -3593,70 +3710,17 @@ struct MsdDriver {
     // are, so a round costs in proportion to the elements still tied, not to n.
     int sort_groups(const uint8_t *flags, int bkey) {
         uint32_t *g_start, *g_len;
-        const unsigned ttiles = (unsigned)std::max<uint64_t>((n + kTieTile - 1) / kTieTile, 1);
-        uint32_t *cf, *cl, *of, *ol;
-        GK_TRY_HIP(c, scratch(c, "tie_cnt_f", ttiles + 1, &cf));
-        GK_TRY_HIP(c, scratch(c, "tie_cnt_l", ttiles + 1, &cl));
-        GK_TRY_HIP(c, scratch(c, "tie_off_f", ttiles + 1, &of));
-        GK_TRY_HIP(c, scratch(c, "tie_off_l", ttiles + 1, &ol));
-        hipLaunchKernelGGL(tie_bounds_kernel<false>, dim3(ttiles), dim3(256), 0, c->stream, flags, n, cf, cl, nullptr,
-                           nullptr, nullptr, nullptr);
-        GK_TRY_HIP(c, hipGetLastError());
-        uint64_t ng = 0, ng2 = 0;
-        GK_TRY_HIP(c, scan_u32_exclusive_pair(c, cf, of, cl, ol, ttiles, &ng, &ng2));
-        if (ng != ng2) return fail(c, GK_E_HIP, "msd: tie group bounds do not pair up");
+        uint64_t ng = 0;
+        if (int rc = tie_groups(flags, &g_start, &g_len, &ng)) return rc;  // (untimed: msd_groups covers the round)
         if (ng == 0) return GK_OK;
-        GK_TRY_HIP(c, scratch(c, "tie_start", ng + 64, &g_start));
-        GK_TRY_HIP(c, scratch(c, "tie_len", ng + 64, &g_len));
-        hipLaunchKernelGGL(tie_bounds_kernel<true>, dim3(ttiles), dim3(256), 0, c->stream, flags, n, nullptr, nullptr,
-                           of, ol, g_start, g_len);
-        GK_TRY_HIP(c, hipGetLastError());
-        hipLaunchKernelGGL(tie_run_lengths_kernel, dim3((unsigned)std::min<uint64_t>((ng + 255) / 256, 8192)),
-                           dim3(256), 0, c->stream, g_start, g_len, ng);
-        GK_TRY_HIP(c, hipGetLastError());
         B = bkey;
         phase = 1;  // (no compact or packed-pair levels: later-phase rules)
-        nd_ready = false;
-        c79_in = false;
-        int rc = classify(ng, 0, 0, cur_big, g_start, g_len, 2);
-        if (rc != GK_OK) return rc;
-        rc = levels(1, 0, 0);
-        if (rc != GK_OK) return rc;
-        return finish();
-    }
-
-    // before another global level: its buckets whose keys are all equal go to the done list
-    // (checked once the big buckets hold few elements: after L1 of a random genome they hold
-    // all of them and never are)
-    int drop_uniform(int level, int out) {
-        if (nbig == 0 || level < 1 || big_elems * 64 > std::max<uint64_t>(c->n, 1)) return GK_OK;
-        uint32_t *mixed;
-        GK_TRY_HIP(c, scratch(c, "uni_mixed", nbig, &mixed));
-        GK_TRY_HIP(c, hipMemsetAsync(mixed, 0, 4ull * nbig, c->stream));
-        hipLaunchKernelGGL(uniform_flag_kernel, dim3(nbig, bucket_split(nbig)), dim3(256), 0, c->stream,
-                           big_start[cur_big], big_len[cur_big], c->keys[out], mixed);
-        GK_TRY_HIP(c, grow_keep(c, "dn_start", ndone + nbig, ndone, &dn_start));
-        GK_TRY_HIP(c, grow_keep(c, "dn_len", ndone + nbig, ndone, &dn_len));
-        GK_TRY_HIP(c, grow_keep(c, "dn_par", ndone + nbig, ndone, &dn_par));
-        GK_TRY_HIP(c, hipMemsetAsync(ctr + kCtrBig, 0, 4, c->stream));
-        GK_TRY_HIP(c, hipMemsetAsync(sums + kCtrBig, 0, 8, c->stream));
-        GK_TRY_HIP(c, hipMemsetAsync(sums + kSumTiles, 0, 16, c->stream));
-        hipLaunchKernelGGL(route_uniform_kernel, dim3(grid_n(nbig)), dim3(256), 0, c->stream, big_start[cur_big],
-                           big_len[cur_big], big_pref[cur_big], nbig, mixed, lists(0, cur_big ^ 1), out, ctr, sums,
-                           (uint32_t)kPTile, ctiles);
-        GK_TRY_HIP(c, hipGetLastError());
-        cur_big ^= 1;
-        int r = read_ctr();
-        if (r != GK_OK) return r;
-        ndone = h[kCtrDone];
-        nbig = h[kCtrBig];
-        big_elems = hs[kCtrBig];
-        return GK_OK;
+        return sort_tied(g_start, g_len, ng);
     }
 
     // global levels while the next-level list is non-empty; `in` holds the current buffer, hi
     // key bits are sorted
-    // (c79_in carries over: a first level from pieces may have written packed pairs)
+    // (cur_fmt carries over: a first level from pieces may have written packed pairs)
     int levels(int level, int hi, int in) {
         while (nbig > 0) {
             const int out = in ^ 1;
@@ -3672,7 +3736,7 @@ struct MsdDriver {
                                    (uint32_t)kPTile, ctiles, tfirst, cfirst, nch);
                 GK_TRY_HIP(c, hipGetLastError());
             } else {
-                hipLaunchKernelGGL(seg_counts_kernel, dim3(grid_n(nbig)), dim3(256), 0, c->stream, big_len[cur_big],
+                hipLaunchKernelGGL(seg_counts_kernel, dim3(grid256_min1(nbig)), dim3(256), 0, c->stream, big_len[cur_big],
                                    nbig, (uint32_t)kPTile, ctiles, ntl, nch);
                 GK_TRY_HIP(c, hipGetLastError());
                 GK_TRY_HIP(c, scan_u32_exclusive_pair_launch(c, ntl, tfirst, nch, cfirst, nbig));
@@ -3700,22 +3764,24 @@ struct MsdDriver {
                             c->vals[in], out);
             if (rc != GK_OK) return rc;
             cur_big ^= 1;
+            const bool pairs_out = cur_fmt == Fmt::Pairs;
             uint64_t before[kLocal];
             for (int k = 0; k < kLocal; ++k) before[k] = nloc[k];
             const uint64_t nsub = (uint64_t)nbig << width(level);
             // the level's input already small: its output's uniform buckets are dropped behind
-            // the classify with one read-back for both (drop_uniform's rule, on the input's size)
-            const bool fuse = !c79_out && level >= 1 && in_big * 64 <= std::max<uint64_t>(c->n, 1) &&
-                              !opt("GKM_NO_FUSED_UNIFORM");
+            // the classify with one read-back for both (few_big_elems on the input's size)
+            const bool fuse = !pairs_out && few_big_elems(level, in_big) && !opt("GKM_NO_FUSED_UNIFORM");
             rc = classify(nsub, hi + width(level), out, cur_big, nullptr, nullptr, 1, big_pref[cur_big ^ 1],
-                          width(level), compact_now ? 1 : 0, !fuse);
+                          width(level), cur_fmt == Fmt::Compact ? 1 : 0, !fuse);
             if (fuse) {
                 const uint64_t bound = std::min<uint64_t>(nsub, in_big / ((uint64_t)kBlockMax + 1));
-                if (rc == GK_OK) rc = bound ? drop_uniform_dev(out, (uint32_t)bound) : classify_counts();
+                if (rc == GK_OK) rc = bound ? route_uniform(out, (uint32_t)bound, true) : classify_counts();
             } else {
-                if (rc == GK_OK && c79_out) rc = expand_pair_locals(before, out);
+                if (rc == GK_OK && pairs_out) rc = expand_pair_locals(before, out);
                 if (rc == GK_OK) rc = expand_big(out);
-                if (rc == GK_OK && !c79_out) rc = drop_uniform(level, out);  // (pairs: keys not comparable)
+                // (pairs: keys not comparable)
+                if (rc == GK_OK && !pairs_out && nbig > 0 && few_big_elems(level, big_elems))
+                    rc = route_uniform(out, nbig, false);
             }
             if (rc != GK_OK) return rc;
             ++level;
@@ -3736,10 +3802,7 @@ struct MsdDriver {
         const CompactIn ci{round == 0 ? loc_pref[k] : nullptr, nd};
         // persistent grids of the workgroups that fit at once (occupancy API, per kernel)
         auto grid = [&](const void *fn, int threads) {
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1)
-                per_cu = 1;
-            uint64_t g = std::min<uint64_t>(cnt, (uint64_t)cus * per_cu);
+            uint64_t g = resident_grid(fn, threads, cnt);
             if (g >= 8) g &= ~7ull;  // the wave kernels' XCD-aware walk
             return dim3((unsigned)g);
         };
@@ -3789,9 +3852,7 @@ struct MsdDriver {
             GK_TRY_HIP(c, grow_keep(c, kLocName[k][1], max_spill, 0, &loc[k][1]));
             pending += nloc[k];
         }
-        GK_TRY_HIP(c, grow_keep(c, "dn_start", ndone + max_spill, ndone, &dn_start));
-        GK_TRY_HIP(c, grow_keep(c, "dn_len", ndone + max_spill, ndone, &dn_len));
-        GK_TRY_HIP(c, grow_keep(c, "dn_par", ndone + max_spill, ndone, &dn_par));
+        if (int rc = grow_done(max_spill)) return rc;
         int g = 0, round = 0;
         while (pending > 0) {
             const int ng = g ^ 1;
@@ -3853,64 +3914,89 @@ struct MsdDriver {
         c->cur = 0;
         return GK_OK;
     }
+
+    // The tail of a sort entry point, behind its first partition: the remaining global levels (from
+    // `level`, hi key bits sorted, buffer `in` current), the local rounds and done copies, the later
+    // phases of multi-word keys; then the total timer ends.  An error stops the work there.
+    // rc: the first partition's result -- entry points that used to end the total timer behind a failed
+    // first partition pass it on, the others return before; open_on_level_error: msd_sort and
+    // msd_shard_sort return from a failed global level at once, with the timer open (kept as it was).
+    int run_from(int rc, int level, int hi, int in, bool open_on_level_error = false) {
+        if (rc == GK_OK) {
+            rc = levels(level, hi, in);
+            if (rc != GK_OK && open_on_level_error) return rc;
+        }
+        if (rc == GK_OK) rc = finish();
+        const int spw = symbols_per_word();
+        for (int ph = 1; ph < phases() && rc == GK_OK; ++ph)
+            rc = next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));
+        timer_end(c, total_slot);
+        return rc;
+    }
+
+    // key-range shards: the ownership-digit histogram of the byte sequence, 2- or 4-bit keys
+    template <int BITS, bool CANON>
+    void hist_launch(const L0Args &a, uint32_t ntiles, uint32_t *gh) {
+        hipLaunchKernelGGL((own_hist_kernel<BITS, CANON>),
+                           dim3(resident_grid((const void *)own_hist_kernel<BITS, CANON>, kST, ntiles)), dim3(kST), 0,
+                           c->stream, a, ntiles, gh);
+    }
+
+    // key-range shards: the single-pass select over the byte sequence -- chunks of *tpw tiles per
+    // workgroup, one region of *tpw * kSTile elements each in keys[1] / vals[1] (room for every
+    // position: no count pass), the chunks' counts in wave_cnt.  Persistent grid = the workgroups that
+    // fit at once (a second round of workgroups would start only when the first ones have walked
+    // all their tiles)
+    template <int BITS, bool CANON>
+    void select_launch(const L0Args &a, Dig d0, uint32_t ntiles, uint32_t *wave_cnt, uint32_t *tpw, uint32_t *nchunk) {
+        const unsigned sgrid = resident_grid((const void *)msd0_select_kernel<BITS, CANON>, kST, ntiles);
+        *tpw = (ntiles + sgrid - 1) / sgrid;
+        *nchunk = (ntiles + *tpw - 1) / *tpw;
+        hipLaunchKernelGGL((msd0_select_kernel<BITS, CANON>), dim3(*nchunk), dim3(kST), 0, c->stream, a, d0, ntiles,
+                           *tpw, wave_cnt, c->keys[1], c->vals[1], nd);
+    }
+
+    // key-range shards: the select's pieces.  Region w of keys[1] / vals[1] starts at w * stride and
+    // holds cnt[w] kept k-mers (cnt on the device, nreg regions); the non-empty ones, in position
+    // order, are the pieces of the first level.  *found: their sum, the stage's units.
+    int harvest_pieces(const uint32_t *cnt, uint64_t nreg, uint64_t stride, int select_slot, std::vector<uint64_t> *poff,
+                       std::vector<uint64_t> *plen, uint64_t *found) {
+        std::vector<uint32_t> kc(nreg);
+        GK_TRY_HIP(c, hipMemcpyAsync(kc.data(), cnt, 4 * nreg, hipMemcpyDeviceToHost, c->stream));
+        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
+        for (uint64_t w = 0; w < nreg; ++w) {
+            if (!kc[w]) continue;
+            poff->push_back(w * stride);
+            plen->push_back(kc[w]);
+            *found += kc[w];
+        }
+        timer_units(c, select_slot, *found);  // (stage rates: kept k-mers out, the whole sequence in)
+        if (*found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
+        return GK_OK;
+    }
 };
 
-// The enumerated k-mers of the whole sequence (gk_sort's fixed-length path, k <= 64).  Keys of
-// more than 64 bits are sorted in phases of one word (64 / bits symbols): phase 0 sorts every
-// k-mer by its first word, each later phase sorts the groups of equal earlier words by the next.
+// The enumerated k-mers of the whole sequence (gk_sort's fixed-length path, k <= 64), in one-word
+// phases (MsdDriver::phases).
 int msd_sort(gk_ctx *c, const KeySpec &ks) {
-    const int spw = 64 / ks.bits;
-    const int nphase = (ks.symbols + spw - 1) / spw;
     MsdDriver d(c, ks);
-    d.B = ks.bits * std::min(ks.symbols, spw);
-    if (nphase == 1) d.enable_wide_l0();
+    int rc = d.begin(c->n);
+    if (rc != GK_OK) return rc;
+    if (d.phases() == 1) d.enable_wide_l0();
     // canonical 2-bit keys with a full 64-bit first word (k >= 32; C5): an 8-bit L0 leaves 48 bits
     // behind the next level -- packed pairs there and a compact level after them, which the 7-bit
     // L0's 49 and 41 bits do not allow (C5 219-221 -> 216.7-216.9 ms, profiles/r4/l08_ab.txt; the
     // same change made C4, 62-bit keys, 5 ms slower)
     if (ks.bits == 2 && ks.canonical && d.B == 64 && !opt("GKM_LEVEL_BITS")) d.wsched[0] = 8;
-    d.allow_c79 = true;
-    d.wkeys = (nphase == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;  // one-word keys end final in keys[0]
-    c->msd_keys_final = d.wkeys != 0;
-    timer_begin(c, "msd_total", &d.total_slot);
-    int rc = d.init(c->n);
-    if (rc != GK_OK) return rc;
-    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {
-        // the packed copy the transfer left beside the sba (gkm_xfer.hip): both L0 passes read 0.37 B
-        // per position instead of packing the bytes in every tile.  Its stops are the non-ACGT bytes:
-        // '$' on an ACGT sba, every byte that ends the ACGT-only k-mers of a mixed one (class A)
-        d.pk_code = c->res_code;
-        d.pk_dol = c->res_dol;
-    }
+    d.use_resident_pack();
     uint64_t found = 0;
-    // the packed L0 output (P88) when the level behind it writes packed pairs
-    d.p88 = d.p88_wanted();  // (multi-word keys: phase 0's first word; the tie phases read keys[0] / vals[0])
-    d.p88_shi = 64 - (d.B - d.width(0) - 8);
-    // The L0's output buffer: the one that makes the last global level write buffer 1, so that the
-    // finishing kernels read buffer 1 and write buffer 0 instead of rewriting buffer 0 in place
-    // (levels predicted from the mean bucket size; C3: L0, L1, L2 -> L0 writes buffer 1).  A/B on
-    // one box (C3, 3 pairs): 67.3-68.3 against 67.7-68.8 ms.
-    int l0b = 0;
-    {
-        uint64_t mean = c->n >> d.width(0);
-        int lev = 0;
-        for (int l = 1; mean > (uint64_t)kBlockMax && l < kMaxLevels; ++l, ++lev) mean >>= d.width(l);
-        l0b = 1 ^ (lev & 1);
-    }
-    rc = d.run_l0(0, c->sba_len, c->keys[l0b], c->vals[l0b], c->elem_cap + 64, &found);
+    rc = d.l0_count(0, c->sba_len, 0, 0xFFFFFFFFu, &found);  // all digits owned
     if (rc != GK_OK) return rc;
     if (found != c->n) return fail(c, GK_E_HIP, "msd: k-mer count differs from the enumeration");
-    rc = d.classify(1u << d.width(0), d.width(0), l0b, 0, nullptr, nullptr, 1, nullptr, d.width(0));
+    int in = 0;
+    rc = d.l0_start(found, &in);
     if (rc != GK_OK) return rc;
-    if (d.p88_in) rc = d.expand_p88_locals(l0b);  // (skewed genomes: L0 buckets finished locally)
-    if (rc != GK_OK) return rc;
-    rc = d.levels(1, d.width(0), l0b);
-    if (rc != GK_OK) return rc;
-    rc = d.finish();
-    for (int ph = 1; ph < nphase && rc == GK_OK; ++ph)
-        rc = d.next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));
-    timer_end(c, d.total_slot);
-    return rc;
+    return d.run_from(GK_OK, 1, d.width(0), in, true);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4102,13 +4188,8 @@ int prefetch_finish(gk_ctx *c, L0Prefetch *p, bool ok) {
 int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks) {
     c->pre_valid = false;  // consumed
     MsdDriver d(c, ks);
-    d.B = ks.total_bits;
     if (d.width(0) != c->pre_w0 || d.width(1) != c->pre_w1) return msd_sort(c, ks);  // (widths changed)
-    d.allow_c79 = true;
-    d.wkeys = (!ks.acgt_only || c->msd_force_keys) ? 1 : 0;  // one-word keys end final in keys[0] (as msd_sort)
-    c->msd_keys_final = d.wkeys != 0;
-    timer_begin(c, "msd_total", &d.total_slot);
-    int rc = d.init(c->n);
+    int rc = d.begin(c->n, ks.total_bits);  // (one word: prefetch_matches)
     if (rc != GK_OK) return rc;
     const uint32_t R = 1u << c->pre_w0, nreg = c->pre_regions;
     uint32_t *pieces;
@@ -4129,18 +4210,15 @@ int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks) {
     if (c->pre_p88_shi) {  // the regions wrote the packed L0 form (its side arrays in vals[1])
         d.p88_place(1);
         d.nd = d.nd_l0;
-        d.p88_in = true;
+        d.cur_fmt = MsdDriver::Fmt::PackedL0;
         d.p88_shi = c->pre_p88_shi;
     } else {
         GK_TRY_HIP(c, scratch(c, "msd_nd", c->sba_len + 64, &d.nd));
+        d.cur_fmt = MsdDriver::Fmt::KeyStartDigit;  // (either way the regions wrote the level-1 digit bytes)
     }
-    d.nd_ready = true;  // the regions' L0 wrote the level-1 digit bytes
     rc = d.first_level_from_pieces(c->keys[1], c->vals[1], poff.data(), plen.data(), pb.data(),
                                    (uint32_t)poff.size(), 1, d.width(0));
-    if (rc == GK_OK) rc = d.levels(2, d.width(0) + d.width(1), 0);
-    if (rc == GK_OK) rc = d.finish();
-    timer_end(c, d.total_slot);
-    return rc;
+    return d.run_from(rc, 2, d.width(0) + d.width(1), 0);
 }
 
 // starts-only shards (GK_SHARD_STARTS_ONLY): key of the k-mer at every received start from the 2-bit
@@ -4159,8 +4237,6 @@ __global__ __launch_bounds__(256) void keys_from_starts_kernel(const uint64_t *_
     }
 }
 
-static unsigned grid_of_n_msd(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
-
 // multi-GPU send side: k-mers starting in [lo, hi) partitioned by their top kGR key bits
 int msd_shard_partition(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uint64_t *kout, uint32_t *vout,
                         uint64_t cap, uint64_t *hist, uint64_t *count) {
@@ -4168,11 +4244,12 @@ int msd_shard_partition(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
     d.B = ks.bits * std::min(ks.symbols, 64 / ks.bits);  // the first key word (see msd_sort)
     d.wsched[0] = kGR;  // the exchange splits by kGR-bit buckets (msd_radix_bits)
     GK_TRY_HIP(c, msd_tables());
-    if (c->res_pk && c->acgt && ks.bits == 2) {  // both L0 passes read the transfer's packed copy
-        d.pk_code = c->res_code;
-        d.pk_dol = c->res_dol;
-    }
-    int rc = d.run_l0(lo, hi, kout, vout, cap, count);
+    // (this test used to read "res_pk && acgt && bits == 2", without "|| ks.acgt_only": the same here,
+    // where the key spec is gk_shard_partition's shard_spec -- acgt_only = 0, and 2-bit keys only
+    // for an ACGT sba)
+    d.use_resident_pack();
+    int rc = d.l0_count(lo, hi, 0, 0xFFFFFFFFu, count);  // all digits owned
+    if (rc == GK_OK) rc = d.l0_partition(kout, vout, cap, *count);
     if (rc != GK_OK) return rc;
     std::vector<uint32_t> hc(kGRadix);
     GK_TRY_HIP(c, hipMemcpyAsync(hc.data(), d.seg_cnt, 4 * kGRadix, hipMemcpyDeviceToHost, c->stream));
@@ -4184,16 +4261,9 @@ int msd_shard_partition(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
 // multi-GPU receive side: sort n received k-mers (buckets as pieces) into keys[0] / vals[0]
 int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint32_t *vin, const uint64_t *poff,
                    const uint64_t *plen, const uint32_t *pbucket, uint32_t np) {
-    const int spw = 64 / ks.bits;
-    const int nphase = (ks.symbols + spw - 1) / spw;
     MsdDriver d(c, ks);
-    d.B = ks.bits * std::min(ks.symbols, spw);
-    d.wkeys = (nphase == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;  // one-word keys end final in keys[0]
-    c->msd_keys_final = d.wkeys != 0;
     d.wsched[0] = kGR;  // pieces are kGR-bit buckets
-    d.allow_c79 = true;
-    timer_begin(c, "msd_total", &d.total_slot);
-    int rc = d.init(c->n);
+    int rc = d.begin(c->n);
     if (rc != GK_OK) return rc;
     if (!kin) {
         // starts only (GK_SHARD_STARTS_ONLY): every received k-mer's key from the rank's own packed copy
@@ -4201,7 +4271,7 @@ int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint
         // words read stay close), with the level-1 digit byte its count pass reads
         const uint64_t *pk = nullptr;
         const uint32_t *pd = nullptr;
-        if (c->res_pk && c->acgt) {
+        if (d.use_resident_pack()) {  // (starts-only shards: an ACGT sba, 2-bit keys -- shard_spec)
             pk = c->res_code;
         } else {
             int rp = pack_sequence(c, &pk, &pd);
@@ -4211,22 +4281,16 @@ int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint
         int slot;
         timer_begin(c, "shard_keys", &slot);
         timer_units(c, slot, c->n);
-        hipLaunchKernelGGL(keys_from_starts_kernel, dim3(grid_of_n_msd(c->n)), dim3(256), 0, c->stream, pk, vin, c->n,
+        hipLaunchKernelGGL(keys_from_starts_kernel, dim3(grid256_cap64k(c->n)), dim3(256), 0, c->stream, pk, vin, c->n,
                            d.B, dig_at(d.B, kGR, d.width(1)), c->keys[1], d.nd);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
         kin = c->keys[1];
-        d.nd_ready = true;
+        d.cur_fmt = MsdDriver::Fmt::KeyStartDigit;
     }
     rc = d.first_level_from_pieces(kin, vin, poff, plen, pbucket, np);
     if (rc != GK_OK) return rc;
-    rc = d.levels(2, kGR + d.width(1), 0);
-    if (rc != GK_OK) return rc;
-    rc = d.finish();
-    for (int ph = 1; ph < nphase && rc == GK_OK; ++ph)
-        rc = d.next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));
-    timer_end(c, d.total_slot);
-    return rc;
+    return d.run_from(GK_OK, 2, kGR + d.width(1), 0, true);
 }
 
 // One-word keys already in memory (keys[cur] / vals[cur], n = c->n; the low total_bits bits of
@@ -4243,9 +4307,6 @@ int msd_sort_keys(gk_ctx *c, int total_bits) {
     kk.words = 1;
     kk.total_bits = total_bits;
     MsdDriver d(c, kk);
-    d.B = total_bits;
-    d.wkeys = 1;
-    d.allow_c79 = true;
     // digit widths: as few global levels as leave buckets of <= ~400 keys for the one-wave
     // finishing classes (1e8 keys: 6 + 6 + 6 bits, buckets of ~380), the bits spread evenly; two
     // 8-bit levels left 1.5 K-key buckets to the block-local class, which ran 3.6 ms for 1e8 keys
@@ -4256,20 +4317,16 @@ int msd_sort_keys(gk_ctx *c, int total_bits) {
         const int w = std::max(6, std::min(8, (b + L - 1) / L));
         for (int l = 0; l < kMaxLevels; ++l) d.wsched[l] = l < L ? w : kGR;
     }
-    c->msd_keys_final = true;
-    timer_begin(c, "msd_total", &d.total_slot);
     const int in = c->cur;
-    int rc = d.init(c->n);
+    int rc = d.begin(c->n, total_bits);  // (one word of up to 8 "symbols": the keys end final in keys[0])
     if (rc != GK_OK) return rc;
     uint32_t *one;
     GK_TRY_HIP(c, scratch(c, "keys_bucket", 2, &one));
     const uint32_t hb[2] = {0, (uint32_t)c->n};
     GK_TRY_HIP(c, hipMemcpyAsync(one, hb, 8, hipMemcpyHostToDevice, c->stream));
     rc = d.classify(1, 0, in, 0, one, one + 1);  // all keys as one bucket, no bits sorted
-    if (rc == GK_OK) rc = d.levels(0, 0, in);
-    if (rc == GK_OK) rc = d.finish();
-    c->cur = 0;
-    timer_end(c, d.total_slot);
+    rc = d.run_from(rc, 0, 0, in);
+    c->cur = 0;  // (whatever the outcome)
     return rc;
 }
 
@@ -4316,15 +4373,12 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
     MsdDriver d(c, ks);
     d.B = ks.bits * std::min(ks.symbols, 64 / ks.bits);  // the first key word (see msd_sort)
     GK_TRY_HIP(c, msd_tables());
-    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
-        d.pk_code = c->res_code;
-        d.pk_dol = c->res_dol;
-    }
+    d.use_resident_pack();
     const int ob = range_own_bits(ks);
     L0Args a{c->sba, lo, std::max(hi, lo), ks.symbols, d.B, ks.acgt_only};
     a.own_bits = ob;
-    a.pk_code = d.pk_code;
-    a.pk_dol = d.pk_dol;
+    a.pk_code = d.l0a.pk_code;
+    a.pk_dol = d.l0a.pk_dol;
     uint32_t *gh;
     GK_TRY_HIP(c, scratch(c, "own_hist", 4096, &gh));
     GK_TRY_HIP(c, hipMemsetAsync(gh, 0, 4 * 4096, c->stream));
@@ -4332,27 +4386,19 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
     int slot;
     timer_begin(c, "histogram", &slot);
     timer_units(c, slot, a.hi - lo);
-#define GK_HIST(B_, C_)                                                                                        \
-    do {                                                                                                       \
-        int per_cu = 0;                                                                                        \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, own_hist_kernel<B_, C_>, kST, 0) !=          \
-                hipSuccess || per_cu < 1)                                                                      \
-            per_cu = 1;                                                                                        \
-        const unsigned g = std::min<unsigned>(ntiles, d.cus * (unsigned)per_cu);                               \
-        hipLaunchKernelGGL((own_hist_kernel<B_, C_>), dim3(g), dim3(kST), 0, c->stream, a, ntiles, gh);        \
-    } while (0)
     if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.hi > lo) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, own_hist_rsel_kernel, kRselW * 64, 0) != hipSuccess ||
-            per_cu < 1)
-            per_cu = 1;
+        const uint64_t resident = (uint64_t)d.cus * resident_per_cu(c, (const void *)own_hist_rsel_kernel, kRselW * 64);
         const uint64_t G = (a.hi + 31) / 32 - lo / 32;
-        const uint64_t gpb = std::max<uint64_t>((G + (uint64_t)d.cus * per_cu - 1) / ((uint64_t)d.cus * per_cu), 1);
+        const uint64_t gpb = std::max<uint64_t>((G + resident - 1) / resident, 1);
         hipLaunchKernelGGL(own_hist_rsel_kernel, dim3((unsigned)((G + gpb - 1) / gpb)), dim3(kRselW * 64), 0, c->stream,
                            a, gpb, gh);
-    } else if (ks.bits == 2) { if (ks.canonical) GK_HIST(2, true); else GK_HIST(2, false); }
-    else { if (ks.canonical) GK_HIST(4, true); else GK_HIST(4, false); }
-#undef GK_HIST
+    } else if (ks.bits == 2) {
+        if (ks.canonical) d.hist_launch<2, true>(a, ntiles, gh);
+        else d.hist_launch<2, false>(a, ntiles, gh);
+    } else {
+        if (ks.canonical) d.hist_launch<4, true>(a, ntiles, gh);
+        else d.hist_launch<4, false>(a, ntiles, gh);
+    }
     GK_TRY_HIP(c, hipGetLastError());
     timer_end(c, slot);
     std::vector<uint32_t> hc(1u << ob);
@@ -4364,100 +4410,68 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
 }
 
 int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t digit_hi, uint64_t *n_kept) {
-    const int spw = 64 / ks.bits;
-    const int nphase = (ks.symbols + spw - 1) / spw;
     MsdDriver d(c, ks);
-    d.B = ks.bits * std::min(ks.symbols, spw);
-    d.wkeys = (nphase == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;  // one-word keys end final in keys[0]
-    c->msd_keys_final = d.wkeys != 0;
-    // packed-pair levels where the bits fit (the first level from the select's pieces has 55 bits
-    // left at C3: its L1 writes the pairs)
-    d.allow_c79 = true;
     d.wsched[0] = range_width(ks);
-    timer_begin(c, "msd_total", &d.total_slot);
+    // (packed-pair levels where the bits fit: the first level from the select's pieces has 55 bits
+    // left at C3, its L1 writes the pairs)
+    int rc = d.begin(MsdDriver::kInitLater);  // (the lists once the select or the count has found n)
+    if (rc != GK_OK) return rc;
     GK_TRY_HIP(c, msd_tables());
     const uint64_t L = c->sba_len;
-    const uint32_t ntiles = (uint32_t)std::max<uint64_t>((L + kSTile - 1) / kSTile, 1);
-    L0Args a{c->sba, 0, L, ks.symbols, d.B, ks.acgt_only};
-    a.own_lo = digit_lo;
-    a.own_span = digit_hi > digit_lo ? digit_hi - digit_lo : 0;
-    a.own_bits = range_own_bits(ks);
-    if (c->res_pk && ks.bits == 2 && (c->acgt || ks.acgt_only)) {  // the transfer's packed copy
-        a.pk_code = c->res_code;
-        a.pk_dol = c->res_dol;
-        d.pk_code = c->res_code;  // (the fused L0 reads it too)
-        d.pk_dol = c->res_dol;
-    }
+    const int ob = range_own_bits(ks);
+    const uint32_t span = digit_hi > digit_lo ? digit_hi - digit_lo : 0;
+    d.use_resident_pack();  // (the select and the fused L0 both read it)
+    c->n = 0;  // nothing in the buffers survives: ensure_elems copies none
+    c->cur = 0;
     // Fused select (round 5): when the rank keeps a large share of the k-mers, its L0 count and
     // partition run over the whole sequence and keep only the owned k-mers (msd0_pipe_kernel<...,
     // OWN>), as msd_sort's L0 does for all of them -- no select pass, no 13-byte write and re-read
     // per kept k-mer, and the packed L0 output.  With a small share the whole-sequence L0 (count,
     // packing and ranking of every position) costs more than the select it replaces.  The share is
     // estimated from the digit range; GKM_RANGE_FUSED=0/1 forces either path.
-    {
-        const int ob = range_own_bits(ks);
-        const uint32_t span = digit_hi > digit_lo ? digit_hi - digit_lo : 0;
-        bool fused = ks.bits == 2 && span > 0 && (uint64_t)span * kFusedMaxRanks >= (1ull << ob);
-        if (const char *e = opt("GKM_RANGE_FUSED")) fused = ks.bits == 2 && span > 0 && e[0] == '1';
-        if (fused) {
-            c->n = 0;
-            c->cur = 0;
-            uint64_t found = 0;
-            int rc = d.l0_count(0, L, digit_lo, span, &found, ob);
-            if (rc != GK_OK) return rc;
-            if (found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
-            *n_kept = found;
-            if (found == 0) {
-                timer_end(c, d.total_slot);
-                return GK_OK;
-            }
-            rc = ensure_elems(c, found + 1, 1);
-            if (rc != GK_OK) return rc;
-            c->n = found;
-            rc = d.init(found);
-            if (rc != GK_OK) return rc;
-            d.p88 = d.p88_wanted();
-            d.p88_shi = 64 - (d.B - d.width(0) - 8);
-            int l0b = 0;  // (as msd_sort: the last global level writes buffer 1)
-            {
-                uint64_t mean = found >> d.width(0);
-                int lev = 0;
-                for (int l = 1; mean > (uint64_t)kBlockMax && l < kMaxLevels; ++l, ++lev) mean >>= d.width(l);
-                l0b = 1 ^ (lev & 1);
-            }
-            rc = d.l0_partition(c->keys[l0b], c->vals[l0b], c->elem_cap + 64, found);
-            if (rc == GK_OK) rc = d.classify(1u << d.width(0), d.width(0), l0b, 0, nullptr, nullptr, 1, nullptr, d.width(0));
-            if (rc == GK_OK && d.p88_in) rc = d.expand_p88_locals(l0b);
-            if (rc == GK_OK) rc = d.levels(1, d.width(0), l0b);
-            if (rc == GK_OK) rc = d.finish();
-            for (int ph = 1; ph < nphase && rc == GK_OK; ++ph)
-                rc = d.next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));
+    bool fused = ks.bits == 2 && span > 0 && (uint64_t)span * kFusedMaxRanks >= (1ull << ob);
+    if (const char *e = opt("GKM_RANGE_FUSED")) fused = ks.bits == 2 && span > 0 && e[0] == '1';
+    if (fused) {
+        uint64_t found = 0;
+        rc = d.l0_count(0, L, digit_lo, span, &found, ob);
+        if (rc != GK_OK) return rc;
+        if (found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
+        *n_kept = found;
+        if (found == 0) {
             timer_end(c, d.total_slot);
-            return rc;
+            return GK_OK;
         }
+        rc = ensure_elems(c, found + 1, 1);
+        if (rc != GK_OK) return rc;
+        c->n = found;
+        rc = d.init(found);
+        if (rc != GK_OK) return rc;
+        int in = 0;
+        rc = d.l0_start(found, &in);
+        return d.run_from(rc, 1, d.width(0), in);
     }
+    const uint32_t ntiles = (uint32_t)std::max<uint64_t>((L + kSTile - 1) / kSTile, 1);
+    L0Args a{c->sba, 0, L, ks.symbols, d.B, ks.acgt_only};
+    a.own_lo = digit_lo;
+    a.own_span = span;
+    a.own_bits = ob;
+    a.pk_code = d.l0a.pk_code;
+    a.pk_dol = d.l0a.pk_dol;
     const Dig d0 = dig_at(d.B, 0, d.width(0));
     uint32_t *wave_cnt;
-    GK_TRY_HIP(c, scratch(c, "sel_wave_cnt", (uint64_t)ntiles + 1, &wave_cnt));
-    c->n = 0;  // nothing in the buffers survives: ensure_elems copies none
-    c->cur = 0;
     int slot;
     uint64_t found = 0;
     std::vector<uint64_t> poff, plen;
     if (ks.bits == 2 && !ks.canonical && a.pk_code && ks.symbols <= 32 && a.own_bits <= 32) {
         // the SWAR select over the packed copy: one region per wave (msd0_rsel_kernel)
         const uint64_t ngroups = (L + 31) / 32;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msd0_rsel_kernel, kRselW * 64, 0) != hipSuccess ||
-            per_cu < 1)
-            per_cu = 1;
-        uint64_t nwv = (uint64_t)d.cus * (unsigned)per_cu * kRselW;
+        uint64_t nwv = (uint64_t)d.cus * resident_per_cu(c, (const void *)msd0_rsel_kernel, kRselW * 64) * kRselW;
         const uint64_t gpw = ((ngroups + nwv - 1) / nwv + 63) / 64 * 64;  // whole 64-group steps per wave
         nwv = (ngroups + gpw - 1) / gpw;
         const unsigned nblk = (unsigned)((nwv + kRselW - 1) / kRselW);
         const uint64_t cap = (uint64_t)nblk * kRselW * gpw * 32;  // every wave region is full-size
         if (cap > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "sequence too long for uint32 start indices");
-        int rc = ensure_elems(c, cap, 1);
+        rc = ensure_elems(c, cap, 1);
         if (rc != GK_OK) return rc;
         GK_TRY_HIP(c, scratch(c, "msd_nd", cap + 64, &d.nd));
         GK_TRY_HIP(c, scratch(c, "sel_wave_cnt", (uint64_t)nblk * kRselW + 1, &wave_cnt));
@@ -4474,63 +4488,27 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
         }
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
-        std::vector<uint32_t> kc(nwv);
-        GK_TRY_HIP(c, hipMemcpyAsync(kc.data(), wave_cnt, 4 * nwv, hipMemcpyDeviceToHost, c->stream));
-        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        for (uint64_t w = 0; w < nwv; ++w) {
-            if (!kc[w]) continue;
-            poff.push_back(w * gpw * 32);
-            plen.push_back(kc[w]);
-            found += kc[w];
-        }
-        timer_units(c, slot, found);
-        if (found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
+        rc = d.harvest_pieces(wave_cnt, nwv, gpw * 32, slot, &poff, &plen, &found);
     } else {
+        // the select over the byte sequence: one region per chunk of tiles (select_launch)
         const uint64_t cap = (uint64_t)ntiles * kSTile;  // every chunk region is full-size
         if (cap > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "sequence too long for uint32 start indices");
-        int rc = ensure_elems(c, cap, 1);
+        rc = ensure_elems(c, cap, 1);
         if (rc != GK_OK) return rc;
         GK_TRY_HIP(c, scratch(c, "msd_nd", cap + 64, &d.nd));
+        GK_TRY_HIP(c, scratch(c, "sel_wave_cnt", (uint64_t)ntiles + 1, &wave_cnt));
         timer_begin(c, "msd_select", &slot);
         timer_units(c, slot, L);
-        // single pass: chunks of tpw tiles per workgroup, one region of tpw * kSTile elements each in
-        // keys[1] / vals[1] (room for every position: no count pass).  Persistent grid = the
-        // workgroups that fit at once (a second round of workgroups would start only when the
-        // first ones have walked all their tiles)
         uint32_t tpw = 1, nchunk = 0;
-#define GK_SEL(B_, C_)                                                                                         \
-    do {                                                                                                       \
-        int per_cu = 0;                                                                                        \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, msd0_select_kernel<B_, C_>, kST, 0) !=       \
-                hipSuccess ||                                                                                  \
-            per_cu < 1)                                                                                        \
-            per_cu = 1;                                                                                        \
-        const unsigned sgrid = std::min<unsigned>(ntiles, d.cus * (unsigned)per_cu);                           \
-        tpw = (ntiles + sgrid - 1) / sgrid;                                                                    \
-        nchunk = (ntiles + tpw - 1) / tpw;                                                                     \
-        hipLaunchKernelGGL((msd0_select_kernel<B_, C_>), dim3(nchunk), dim3(kST), 0, c->stream, a, d0, ntiles, \
-                           tpw, wave_cnt, c->keys[1], c->vals[1], d.nd);                                       \
-    } while (0)
-        if (ks.bits == 2 && ks.canonical) GK_SEL(2, true);
-        else if (ks.bits == 2) GK_SEL(2, false);
-        else if (ks.canonical) GK_SEL(4, true);
-        else GK_SEL(4, false);
-#undef GK_SEL
-        const uint64_t stride = (uint64_t)tpw * kSTile;  // each chunk's region
+        if (ks.bits == 2 && ks.canonical) d.select_launch<2, true>(a, d0, ntiles, wave_cnt, &tpw, &nchunk);
+        else if (ks.bits == 2) d.select_launch<2, false>(a, d0, ntiles, wave_cnt, &tpw, &nchunk);
+        else if (ks.canonical) d.select_launch<4, true>(a, d0, ntiles, wave_cnt, &tpw, &nchunk);
+        else d.select_launch<4, false>(a, d0, ntiles, wave_cnt, &tpw, &nchunk);
         GK_TRY_HIP(c, hipGetLastError());
         timer_end(c, slot);
-        std::vector<uint32_t> kc(nchunk);
-        GK_TRY_HIP(c, hipMemcpyAsync(kc.data(), wave_cnt, 4 * (uint64_t)nchunk, hipMemcpyDeviceToHost, c->stream));
-        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        for (uint32_t w = 0; w < nchunk; ++w) {
-            if (!kc[w]) continue;
-            poff.push_back((uint64_t)w * stride);
-            plen.push_back(kc[w]);
-            found += kc[w];
-        }
-        timer_units(c, slot, found);  // (stage rates: kept k-mers out, the whole sequence in)
-        if (found > 0xFFFFFFFFull) return fail(c, GK_E_ARG, "more k-mers than uint32 start indices can address");
+        rc = d.harvest_pieces(wave_cnt, nchunk, (uint64_t)tpw * kSTile, slot, &poff, &plen, &found);
     }
+    if (rc != GK_OK) return rc;
     *n_kept = found;
     c->n = found;
     if (found == 0) {
@@ -4538,21 +4516,16 @@ int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t dig
         return GK_OK;
     }
     uint8_t *nd_keep = d.nd;
-    int rc = d.init(found);
+    rc = d.init(found);
     if (rc != GK_OK) return rc;
     d.nd = nd_keep;
-    d.nd_ready = true;  // the select wrote the L0 digit bytes
+    d.cur_fmt = MsdDriver::Fmt::KeyStartDigit;  // the select wrote the L0 digit bytes
     // the chunks' regions of keys[1] / vals[1] are the pieces of one bucket, in position order;
     // the first level partitions them into [0, found) of keys[0] / vals[0]
     const std::vector<uint32_t> pb(poff.size(), 0u);
     rc = d.first_level_from_pieces(c->keys[1], c->vals[1], poff.data(), plen.data(), pb.data(), (uint32_t)poff.size(),
                                    0, 0);
-    if (rc == GK_OK) rc = d.levels(1, d.width(0), 0);
-    if (rc == GK_OK) rc = d.finish();
-    for (int ph = 1; ph < nphase && rc == GK_OK; ++ph)
-        rc = d.next_phase(ph * spw, std::min(spw, ks.symbols - ph * spw));
-    timer_end(c, d.total_slot);
-    return rc;
+    return d.run_from(rc, 1, d.width(0), 0);
 }
 
 }  // namespace gkm
