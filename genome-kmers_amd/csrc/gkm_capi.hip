@@ -47,6 +47,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_TEST_VMM_MIN_KB", false},
     // gk_lookup (gkm_lookup.hip): forced path (bytes | keys), queries per launch, directory off (0)
     {"GKM_LOOKUP_PATH", false},     {"GKM_LOOKUP_CHUNK", false},    {"GKM_LOOKUP_DIR", false},
+    // gk_lookup_mismatch (gkm_mismatch.hip): forced path (bytes | keys), queries per launch
+    {"GKM_MISMATCH_PATH", false},   {"GKM_MISMATCH_CHUNK", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)

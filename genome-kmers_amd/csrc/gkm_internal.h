@@ -355,6 +355,27 @@ __device__ __forceinline__ uint64_t seg_end_of(const uint32_t *__restrict__ seg,
 }
 constexpr uint64_t kMsdKeysMin = 1ull << 20;
 
+// gk_lookup / gk_lookup_mismatch (gkm_lookup.hip, gkm_mismatch.hip)
+// 4-bit symbol code of byte b (gkm_canon.h: '$' and anything else 0, A B C D G H K M N R S T V W Y ->
+// 1..15), computed rather than read from a table in constant memory: each block fills its 256-byte
+// LDS copy once, one byte per thread, so there is no per-device upload to keep track of
+__device__ __forceinline__ uint8_t lookup_code4(uint32_t b) {
+    constexpr char kOrder[] = "ABCDGHKMNRSTVWY";
+    uint8_t code = 0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i)
+        if (b == (uint32_t)kOrder[i]) code = (uint8_t)(i + 1);
+    return code;
+}
+
+// the context holds final one-word 2-bit forward keys in sorted order (no re-encode is triggered)
+inline bool lookup_keys_usable(const gk_ctx *c) {
+    const KeySpec &ks = c->spec;
+    return c->n >= 1 && c->keys_valid && !c->keys_stale && !c->keys_are_ranks && !c->canonical && ks.bits == 2 &&
+           ks.words == 1 && ks.lenbits == 0 && !ks.canonical && !ks.acgt_only && ks.symbols >= 1 &&
+           ks.symbols <= 32 && (uint32_t)ks.symbols == c->sort_len && c->keys[c->cur] != nullptr;
+}
+
 // group / scan
 hipError_t select_flags(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint64_t *count);
 hipError_t select_flags_counts(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint32_t *out_cnt,

@@ -22,18 +22,6 @@
 
 namespace gkm {
 
-// 4-bit symbol code of byte b (gkm_canon.h: '$' and anything else 0, A B C D G H K M N R S T V W Y ->
-// 1..15), computed rather than read from a table in constant memory: each block fills its 256-byte
-// LDS copy once, one byte per thread, so there is no per-device upload to keep track of
-__device__ __forceinline__ uint8_t lookup_code4(uint32_t b) {
-    constexpr char kOrder[] = "ABCDGHKMNRSTVWY";
-    uint8_t code = 0;
-#pragma unroll
-    for (int i = 0; i < 15; ++i)
-        if (b == (uint32_t)kOrder[i]) code = (uint8_t)(i + 1);
-    return code;
-}
-
 constexpr int kLookupThreads = 256;
 constexpr int kLookupMaxBlocks = 2048;      // 8 blocks per CU; the rest by grid stride
 constexpr uint32_t kLookupLdsQlen = 192;    // longer queries stay in device memory (48 KiB of LDS per block)
@@ -159,14 +147,6 @@ __global__ __launch_bounds__(kLookupThreads) void lookup_keys_kernel(
 static unsigned lookup_grid(uint64_t items) {
     const uint64_t g = (items + kLookupThreads - 1) / kLookupThreads;
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(g, 1), kLookupMaxBlocks);
-}
-
-// the context holds final one-word 2-bit forward keys in sorted order (no re-encode is triggered)
-static bool lookup_keys_usable(const gk_ctx *c) {
-    const KeySpec &ks = c->spec;
-    return c->n >= 1 && c->keys_valid && !c->keys_stale && !c->keys_are_ranks && !c->canonical && ks.bits == 2 &&
-           ks.words == 1 && ks.lenbits == 0 && !ks.canonical && !ks.acgt_only && ks.symbols >= 1 &&
-           ks.symbols <= 32 && (uint32_t)ks.symbols == c->sort_len && c->keys[c->cur] != nullptr;
 }
 
 static int lookup_build_dir(gk_ctx *c, uint32_t **out) {

@@ -57,12 +57,13 @@ EXPORTED = (
     "gk_shard_histogram", "gk_shard_sort_range", "gk_shard_class_b", "gk_shard_class_b_copy",
     "gk_shard_sort_range_b", "gk_rank_mode", "gk_reference_random_bases",
     "gk_copy_sequence", "gk_sort_hint", "gk_resident_packed", "gk_set_option",
-    "gk_lookup", "gk_copy_strand_range",
+    "gk_lookup", "gk_copy_strand_range", "gk_lookup_mismatch",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
 SORT_QUICKSORT_ORDER = 2  # GK_SORT_QUICKSORT_ORDER
 SHARD_STARTS_ONLY = 4  # GK_SHARD_STARTS_ONLY
+MISMATCH_BOTH_STRANDS = 1  # GK_MISMATCH_BOTH_STRANDS
 
 
 class GkFilter(ctypes.Structure):
@@ -153,6 +154,8 @@ _SIGS = {
     "gk_resident_packed": ([_P, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "gk_set_option": ([ctypes.c_char_p, ctypes.c_char_p], ctypes.c_int),
     "gk_lookup": ([_P, _U8P, ctypes.c_uint64, ctypes.c_uint32, _U64P, _U32P], ctypes.c_int),
+    "gk_lookup_mismatch": ([_P, _U8P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U64P, _U32P,
+                            _U64P, _U8P, _U8P, ctypes.c_uint64, _U64P], ctypes.c_int),
     "gk_copy_strand_range": ([_P, ctypes.c_uint64, _U8P, ctypes.c_uint64], ctypes.c_int),
 }
 
@@ -528,6 +531,51 @@ class Engine:
             self._check(self.lib.gk_lookup(self.ctx, _ptr(q, ctypes.c_uint8), m, qlen, _ptr(first, ctypes.c_uint64),
                                            _ptr(count, ctypes.c_uint32)))
         return first, count
+
+    def _mismatch_args(self, queries, max_mismatches, both_strands):
+        q = np.ascontiguousarray(queries, dtype=np.uint8)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be a 2-D uint8 array (ndim = {q.ndim})")
+        if max_mismatches < 0:
+            raise ValueError(f"max_mismatches ({max_mismatches}) must be >= 0")
+        return q, (MISMATCH_BOTH_STRANDS if both_strands else 0)
+
+    def mismatch_counts(self, queries: np.ndarray, max_mismatches: int, both_strands: bool = False) -> np.ndarray:
+        """uint64[m, max_mismatches + 1]: for each query of a pack_queries batch [m, q] the number of
+        (position of the current order, strand) pairs at each distance 0..max_mismatches
+        (gk_lookup_mismatch, counts only)."""
+        q, flags = self._mismatch_args(queries, max_mismatches, both_strands)
+        m, qlen = q.shape
+        counts = np.zeros((m, int(max_mismatches) + 1), dtype=np.uint64)
+        total = ctypes.c_uint64(0)
+        if m:
+            self._check(self.lib.gk_lookup_mismatch(self.ctx, _ptr(q, ctypes.c_uint8), m, qlen, int(max_mismatches),
+                                                    flags, _ptr(counts, ctypes.c_uint64), None, None, None, None, 0,
+                                                    ctypes.byref(total)))
+        return counts
+
+    def mismatch_hits(self, queries: np.ndarray, max_mismatches: int, both_strands: bool = False,
+                      max_hits: int = 1 << 26):
+        """(counts, query uint32[h], kmer_num uint64[h], mismatches uint8[h], strand uint8[h]): the
+        hits of gk_lookup_mismatch in ascending (query, kmer_num, strand), by a counts call and then a
+        hits call.  ValueError (naming the total) when there are more than max_hits."""
+        q, flags = self._mismatch_args(queries, max_mismatches, both_strands)
+        m, qlen = q.shape
+        counts = self.mismatch_counts(q, max_mismatches, both_strands)
+        h = int(counts.sum())
+        if h > max_hits:
+            raise ValueError(f"the search has {h} hits, more than max_hits ({max_hits})")
+        query = np.empty(h, dtype=np.uint32)
+        num = np.empty(h, dtype=np.uint64)
+        mism = np.empty(h, dtype=np.uint8)
+        strand = np.empty(h, dtype=np.uint8)
+        total = ctypes.c_uint64(0)
+        if h:
+            self._check(self.lib.gk_lookup_mismatch(self.ctx, _ptr(q, ctypes.c_uint8), m, qlen, int(max_mismatches),
+                                                    flags, _ptr(counts, ctypes.c_uint64), _ptr(query, ctypes.c_uint32),
+                                                    _ptr(num, ctypes.c_uint64), _ptr(mism, ctypes.c_uint8),
+                                                    _ptr(strand, ctypes.c_uint8), h, ctypes.byref(total)))
+        return counts, query, num, mism, strand
 
     def strand_range(self, offset: int, count: int) -> np.ndarray:
         """copy_strands for the sorted positions [offset, offset + count) (gk_copy_strand_range)."""

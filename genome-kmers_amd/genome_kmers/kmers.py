@@ -755,6 +755,56 @@ class Kmers:
             strands = [strand_char] * count
         return [(st, names[sg], sq) for st, sg, sq in zip(strands, seg.tolist(), seq_idx.tolist())]
 
+    # ---- search with mismatches (no reference counterpart) -------------------------------------
+    def _near_queries(self, kmers, max_mismatches):
+        self._check_forward()
+        q = _native.pack_queries(kmers)
+        if q.shape[0]:
+            qlen = q.shape[1]
+            if qlen > 32:
+                raise ValueError(f"the k-mers have {qlen} characters, more than 32")
+            if max_mismatches > qlen:
+                raise ValueError(f"max_mismatches ({max_mismatches}) is greater than the k-mers' length ({qlen})")
+        if max_mismatches < 0:
+            raise ValueError(f"max_mismatches ({max_mismatches}) must be >= 0")
+        self._sync_device()
+        return q
+
+    def count_near(self, kmers, max_mismatches: int, both_strands: bool = False) -> np.ndarray:
+        """How many k-mers lie within ``max_mismatches`` substitutions of each given k-mer, by distance:
+        a scan of every position of the current order on the GPU (gk_lookup_mismatch; no sort needed).
+
+        ``kmers`` as in find (q <= 32 characters).  Returns uint64 ``[m, max_mismatches + 1]``
+        (1-D for a single ``str`` / ``bytes``): entry d counts the positions whose first q bytes hold
+        no '$' and differ from the query in exactly d places (plain byte inequality: 'N' matches
+        only 'N').  ``both_strands``: the reverse complement of the query is compared too, and a
+        position counts once per strand on which it qualifies."""
+        single = isinstance(kmers, (str, bytes, bytearray))
+        q = self._near_queries(kmers, max_mismatches)
+        counts = self._engine.mismatch_counts(q, max_mismatches, both_strands)
+        return counts[0] if single else counts
+
+    def find_near(self, kmers, max_mismatches: int, both_strands: bool = False, max_hits: int = 1 << 26) -> tuple:
+        """The hits behind count_near: arrays ``(query, kmer_num, mismatches, strand)`` in ascending
+        (query, kmer_num, strand).  ``kmer_num`` is the position in the order currently held (as in
+        get_kmers); ``strand`` is 0 for the query as given, 1 for its reverse complement.  ValueError
+        naming the total when there are more than ``max_hits`` hits."""
+        q = self._near_queries(kmers, max_mismatches)
+        return self._engine.mismatch_hits(q, max_mismatches, both_strands, max_hits)[1:]
+
+    def get_near_locations(self, kmer, max_mismatches: int, both_strands: bool = False,
+                           one_based_seq_index: bool = False) -> list:
+        """[(strand, record_name, seq_idx, mismatches)] of every hit of one k-mer, in find_near's
+        order; strand "-" where the reverse complement of the k-mer sits at that forward position."""
+        if not isinstance(kmer, (str, bytes, bytearray)):
+            raise ValueError("get_near_locations takes one k-mer (str or bytes)")
+        _, nums, mism, strand = self.find_near(kmer, max_mismatches, both_strands)
+        if len(nums) == 0:
+            return []
+        _, _, names, seg, _, _, seq_idx = self._locate_records(nums, one_based_seq_index)
+        return [("-" if st else "+", names[sg], sq, mm)
+                for st, sg, sq, mm in zip(strand.tolist(), seg.tolist(), seq_idx.tolist(), mism.tolist())]
+
     def get_encoded_kmers(self) -> np.ndarray:
         """Encoded keys of the sorted k-mers, one row per k-mer."""
         if not self._is_sorted:

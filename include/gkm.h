@@ -314,6 +314,37 @@ int gk_locate(gk_ctx *ctx, const uint64_t *kmer_nums, uint64_t m, uint32_t *sba_
  * message names the query and the byte).  m == 0 returns GK_OK and touches nothing. */
 int gk_lookup(gk_ctx *ctx, const uint8_t *queries, uint64_t m, uint32_t qlen, uint64_t *first, uint32_t *count);
 
+/* K-mer search with mismatches (no reference routine: the reference offers no search; "end of contig"
+ * is its comparator's, kmers.py:306-397).  A scan, not a search: every position of the CURRENT
+ * start-index order -- sorted, unsorted, canonical, a shard's, or one given with gk_set_start_indices;
+ * no sort is needed -- is compared with every query.  queries: m x qlen ASCII bytes, row-major, host
+ * memory, letters of the sba alphabet without '$' (gk_lookup's rule and GK_E_ALPHABET message).
+ * Position i takes part when the qlen bytes at starts[i] hold no '$' and do not run past the end (a
+ * k-mer that meets its contig's end first matches at no distance, as it never matches in gk_lookup);
+ * its distance to query j is the number of byte positions that differ, by plain byte inequality ('N'
+ * against 'A' is a mismatch, 'N' against 'N' a match: no IUPAC compatibility).  With
+ * GK_MISMATCH_BOTH_STRANDS each position is also compared with the reverse complement of the query
+ * (the reference's IUPAC complement, sequence_collection.py:402-433) -- the reverse complement of the
+ * k-mer against the query -- reported as strand 1, the query as given as strand 0; a position that
+ * qualifies on both strands is reported on both.
+ * counts[j * (max_mismatches + 1) + d] = the number of (position, strand) pairs at distance exactly d
+ * from query j, d in [0, max_mismatches]; *n_hits = their sum, always written.  Hits in two calls, as
+ * gk_group_members: with hit_query == NULL only counts and *n_hits; otherwise all four hit arrays
+ * are non-null and capacity >= *n_hits (the device's record buffer is sized from the hits found, not
+ * from capacity: a search with more than 2^20 hits scans twice), and hit t is query hit_query[t] against position hit_kmer_num[t] of the
+ * current order (gk_locate's numbering) at distance hit_mismatches[t] on strand hit_strand[t], in
+ * ascending (query, kmer_num, strand) whatever the device's scheduling.  1 <= qlen <= 32,
+ * max_mismatches <= qlen, m <= 2^32 (hit_query is 32 bits wide); qlen is not tied to the sort length.
+ * Synchronises the stream.
+ * GK_E_ARG: a null context, null queries / counts / n_hits / hit arrays, qlen or max_mismatches out of
+ * range, m > 2^32, unknown flag bits, capacity < *n_hits (the message names the number); GK_E_STATE: no
+ * sequence or no start indices; GK_E_ALPHABET: a query byte outside the alphabet.  m == 0 returns
+ * GK_OK with *n_hits = 0 and touches nothing else. */
+#define GK_MISMATCH_BOTH_STRANDS 1u
+int gk_lookup_mismatch(gk_ctx *ctx, const uint8_t *queries, uint64_t m, uint32_t qlen, uint32_t max_mismatches,
+                       uint32_t flags, uint64_t *counts, uint32_t *hit_query, uint64_t *hit_kmer_num,
+                       uint8_t *hit_mismatches, uint8_t *hit_strand, uint64_t capacity, uint64_t *n_hits);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
