@@ -66,7 +66,7 @@ def check_canonical(seqs, k, user_starts=None):
     return km, sc
 
 
-@pytest.mark.parametrize("k", [1, 5, 21, 31, 32, 33, 63, 64, 100])
+@pytest.mark.parametrize("k", [1, 5, 21, 31, 32, 33, 56, 57, 63, 64, 100])
 def test_canonical_acgt_vs_oracle(k):
     rng = np.random.default_rng(300 + k)
     check_canonical(genome_with_rc_repeats(rng, [40_000, 12_000, 200], b"ACGT"), k)

@@ -279,7 +279,7 @@ def test_iupac_k31_vs_oracle():
     oracle_check(random_genome(rng, [120_000, 60_000], alphabet=b"ACGTACGTACGTNRY"), 31, 31)
 
 
-@pytest.mark.parametrize("k", [1, 2, 5, 16, 32, 33, 63, 64, 100])
+@pytest.mark.parametrize("k", [1, 2, 5, 16, 32, 33, 55, 56, 57, 63, 64, 100])
 def test_k_sweep_vs_oracle(k):
     rng = np.random.default_rng(100 + k)
     oracle_check(random_genome(rng, [40_000, 9_000, 128]), k, k)
@@ -289,7 +289,7 @@ def test_k_sweep_vs_oracle(k):
 # each group of equal earlier words by the next word (gkm_msd.hip next_phase).  Planted repeats
 # make groups that tie on one and on every word.
 @pytest.mark.parametrize("alphabet", [b"ACGT", b"ACGTACGTACGTNRY"])
-@pytest.mark.parametrize("k", [17, 33, 40, 63, 64])
+@pytest.mark.parametrize("k", [17, 33, 40, 55, 56, 57, 63, 64])
 def test_multiword_repeats_vs_oracle(alphabet, k):
     rng = np.random.default_rng(200 + k + len(alphabet))
     rep = rng.choice(np.frombuffer(alphabet, dtype=np.uint8), 3000).astype(np.uint8)
