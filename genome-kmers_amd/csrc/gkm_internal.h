@@ -190,7 +190,7 @@ struct gk_ctx {
     bool pre_valid = false;          // keys[1] / vals[1] / scratch "msd_nd" + "pre_pieces" hold it
     uint32_t pre_k = 0, pre_regions = 0;
     int pre_w0 = 0, pre_w1 = 0;
-    int pre_p88_shi = 0;             // != 0: the regions wrote the packed L0 form (gkm_msd.hip P88)
+    int pre_p88_shi = 0;             // != 0: the regions wrote the packed L0 form (gkm_msd_l0.h P88)
 
     // profiling
     bool profile = false;
@@ -225,7 +225,7 @@ constexpr int kHostPinWords = 64;
 // copy `bytes` (<= 8 * kHostPinWords) from device memory to `host` through the context's pinned
 // words, after everything enqueued on c->stream before it (synchronises the stream)
 hipError_t read_back(gk_ctx *c, const void *dev, size_t bytes, void *host);
-// pack2_kernel (gkm_msd.hip) over nwords words of 32 bytes from `from`
+// pack2_kernel (gkm_msd_l0.h) over nwords words of 32 bytes from `from`
 hipError_t launch_pack2(const uint8_t *from, uint64_t nwords, uint64_t *code, uint32_t *dol, hipStream_t s);
 // grow-only named device scratch buffer of at least `bytes` (contents not preserved on growth)
 template <typename T>
@@ -381,6 +381,14 @@ hipError_t select_flags(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *o
 hipError_t select_flags_counts(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint32_t *out_cnt,
                                uint64_t *count);
 hipError_t scan_flags_inclusive(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out);
+// exclusive scan of n entries; *total = their sum (one host round trip)
+hipError_t scan_u32_exclusive_pub(gk_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *total);
+// two exclusive scans of n entries with one host round trip for both totals
+hipError_t scan_u32_exclusive_pair(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
+                                   uint32_t *out2, uint64_t n, uint64_t *total1, uint64_t *total2);
+// two exclusive scans of n entries, no read-back (the caller knows the totals)
+hipError_t scan_u32_exclusive_pair_launch(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
+                                          uint32_t *out2, uint64_t n);
 
 // write the lazily enumerated starts into vals[cur] if a reader needs them (gkm_capi.hip)
 int materialize_starts(gk_ctx *c);

@@ -16,6 +16,10 @@
 // keys stay in start order without ever comparing starts; a sub-bucket whose key bits are
 // exhausted is final as it stands.  Every global partition offset is known before its scatter
 // starts (count pass + column scan of per-tile digit histograms): no look-back chain.
+//
+// This file is the host side: the driver (MsdDriver) and the entry points.  The kernels are in the
+// stage headers included below (gkm_msd_l0.h, _scan.h, _lists.h, _local.h, _ties.h), their constants
+// in gkm_msd_config.h.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -23,56 +27,11 @@
 
 #include "gkm_canon.h"
 #include "gkm_internal.h"
+#include "gkm_msd_config.h"
 #include "gkm_partition.h"
 #include "gkm_swar.h"
 
 namespace gkm {
-
-constexpr int kGR = 8;                  // global digit bits
-constexpr int kGRadix = 1 << kGR;
-// global partition tile: 1024 threads x 11 keys (tuning overrides GKM_PT / GKM_PI: tools/build_variant.sh)
-#ifndef GKM_PT
-#define GKM_PT 1024
-#endif
-#ifndef GKM_PI
-#define GKM_PI 11
-#endif
-constexpr int kPT = GKM_PT, kPI = GKM_PI;
-// wide L0 (msd0_wide_kernel): 11-bit digits over 18,432-position tiles of its own, 512 threads x 36
-constexpr int kWideL0 = 11, kWT = 512, kWI = 36;
-constexpr int kPTile = kPT * kPI;
-constexpr int kChunkTiles = 256;        // tiles per scan chunk (GKM_TEST_CHUNK_TILES overrides: tests only)
-constexpr int kBT = 512, kBI = 8, kBR = 8;    // block-local: 512 threads x 8 keys, 8-bit digit
-constexpr int kBT2 = 1024, kBR2 = 10;         // big block-local: 1024 threads x 8 keys, 10-bit digit
-                                              // (~5.9 K keys over 1024 digits: sub-buckets of ~6,
-                                              // finished by rank-by-count, few re-listed)
-constexpr int kBlockMax = kBT2 * kBI;   // 8192: larger buckets take another global level
-// local finishing classes by bucket size: one wave x 4, 8 or 16 keys (msd_wave_kernel), 512
-// threads x 8 keys (msd_local_kernel, <= 4096), 4 = tiny (<= kTiny elements: one thread per
-// bucket), 5 = 1024 threads x 8 keys (<= 8192: the buckets an 11-bit L0 + one level leave at C3)
-constexpr int kLocal = 6;
-constexpr int kTiny = 8;
-constexpr int kSmall = 24;                  // sub-buckets <= this: rank-by-count
-// waves per SIMD the wave-local kernels' registers are capped for (msd_wave_kernel<I, W, .>); the
-// LDS (7.2 KB per wave at I = 8) admits 5 per SIMD
-#ifndef GKM_WAVE_OCC8
-#define GKM_WAVE_OCC8 4
-#endif
-constexpr int kWaveOcc4 = 6, kWaveOcc8 = GKM_WAVE_OCC8, kWaveOcc16 = 3;
-// digit bits of the wave-local kernels' in-LDS partition: buckets of ~370 keys (C3) over 512
-// digits leave sub-buckets of ~0.7 keys (rank-by-count reads half of what 256 digits need)
-#ifndef GKM_WAVE_R8
-#define GKM_WAVE_R8 9
-#endif
-constexpr int kWaveR4 = 8, kWaveR8 = GKM_WAVE_R8, kWaveR16 = 10;
-// later local rounds (buckets re-listed because a sub-bucket outgrew kSmall: repeat families) and
-// later phases finish sub-buckets of up to kSmallLate by rank-by-count instead of re-listing them
-// for another round -- a round costs a bucket load, ranking and write-back per bucket
-constexpr int kSmallLate = 96;
-// The local rounds write back the keys of a bucket only when some of its elements are re-listed
-// (rare): the sort's product is the start order (+ group heads), and keys are re-encoded from the
-// sorted starts when an API call needs them (gk_ctx::keys_stale).
-constexpr int kMaxLevels = 16;              // global levels with a digit width of their own (wsched)
 
 __constant__ uint8_t c_code4_msd[256];
 static bool g_msd_tables = false;
@@ -87,2555 +46,16 @@ static hipError_t msd_tables() {
     return e;
 }
 
-// ---------------------------------------------------------------------------------------------
-// L0: keys straight from the sequence byte array
-// ---------------------------------------------------------------------------------------------
-// A tile's bases are first packed into LDS: symbol codes MSB-first (64/BITS per word) and a '$'
-// bitmask (32 positions per word).  The key of position p is then one funnel shift of two code
-// words, and p is a valid start iff the S mask bits from p are all zero ('$' ends a contig; the
-// pad after the array is '$').
-struct L0Args {
-    const uint8_t *sba;
-    uint64_t lo, hi;  // k-mer starts in [lo, hi) (lo a multiple of 32: 16-B aligned tiles)
-    int symbols, total_bits;
-    int acgt_only;    // 2-bit keys of a mixed sba: k-mers holding a non-ACGT byte are not started
-    // key-range shard: only k-mers whose ownership digit o (the top own_bits key bits) has
-    // o - own_lo < own_span are kept (all: 0, ~0)
-    uint32_t own_lo = 0, own_span = 0xFFFFFFFFu;
-    int own_bits = 7;
-    // 2-bit packed copy of an ACGT sba (pack2_kernel, 32 positions per word; null: pack bytes)
-    const uint64_t *pk_code = nullptr;
-    const uint32_t *pk_dol = nullptr;
-    // unused: holds the place of a removed profiling pointer.  Every L0 kernel takes this struct by
-    // value, and dropping the 8 bytes moves the kernel arguments behind it, which changed the
-    // register allocation of the tuned kernels (other SGPR spill counts in msd0_pipe_kernel); to be
-    // removed together with an A/B run of the L0 passes
-    uint64_t reserved = 0;
-};
-
-__device__ __forceinline__ bool l0_owned(uint32_t d, const L0Args &a) { return d - a.own_lo < a.own_span; }
-// the ownership digit of a total_bits-bit key (own_bits <= total_bits)
-__device__ __forceinline__ bool l0_owned_key(uint64_t key, const L0Args &a) {
-    return l0_owned((uint32_t)(key >> (a.total_bits - a.own_bits)), a);
-}
-
-template <int BITS, int TILE>
-struct L0Pack {
-    static constexpr int kGroups = TILE / 32 + 3;             // 32-position groups packed (k <= 64)
-    static constexpr int kCodeWords = kGroups * BITS / 2 + 1;  // u64 words (+1 for the funnel)
-};
-
-// The tile's bytes (kGroups * 32, incl. the halo) in 8-byte units, spread over all T threads:
-// thread t holds units t, t + T, ... (kPer registers; index clamped so the loads stay branch-free)
-template <int BITS, int TILE, int T>
-struct L0Units {
-    static constexpr int kUnits = L0Pack<BITS, TILE>::kGroups * 4;
-    static constexpr int kPer = (kUnits + T - 1) / T;
-};
-
-template <int BITS, int TILE, int T>
-__device__ __forceinline__ void l0_load(const L0Args &a, uint64_t P0, uint64_t (&r)[L0Units<BITS, TILE, T>::kPer]) {
-    using U = L0Units<BITS, TILE, T>;
-    static_assert(U::kPer >= 2, "the packed path keeps a code word and a stop word");
-    // every element of r is written on both paths (a path that leaves some unwritten made the
-    // compiler keep r in scratch memory at kPer = 3)
-    if (BITS == 2 && a.pk_code) {  // pre-packed: thread t holds the words of groups t, t + T, ...
-        constexpr int kPairs = U::kPer / 2;
-        static_assert(kPairs * T >= L0Pack<BITS, TILE>::kGroups, "every packed group has a register pair");
-#pragma unroll
-        for (int j = 0; j < kPairs; ++j) {
-            const uint64_t g = (P0 >> 5) + min((uint32_t)(threadIdx.x + j * T), (uint32_t)L0Pack<BITS, TILE>::kGroups - 1);
-            r[2 * j] = a.pk_code[g];
-            r[2 * j + 1] = a.pk_dol[g];
-        }
-#pragma unroll
-        for (int j = 2 * kPairs; j < U::kPer; ++j) r[j] = 0;
-    } else {
-        const uint64_t *s8 = reinterpret_cast<const uint64_t *>(a.sba + P0);
-#pragma unroll
-        for (int j = 0; j < U::kPer; ++j) r[j] = s8[min((uint32_t)(threadIdx.x + j * T), (uint32_t)U::kUnits - 1)];
-    }
-}
-
-// 2-bit codes (A0 C1 G2 T3) of 8 bytes as 16 bits, position 0 in the most significant pair
-__device__ __forceinline__ uint32_t pack2_8(uint64_t x) {
-    uint64_t t = __builtin_bswap64(((x >> 1) ^ (x >> 2)) & 0x0303030303030303ull);
-    t = (t | (t >> 6)) & 0x000F000F000F000Full;
-    t = (t | (t >> 12)) & 0x000000FF000000FFull;
-    return (uint32_t)((t | (t >> 24)) & 0xFFFFu);
-}
-
-// s_dol bit = the position ends k-mers: '$' (or, acgt_only, any byte outside ACGT).  Every thread
-// packs its 8-byte units: 2-bit codes into 16-bit (4-bit: 32-bit) pieces of the MSB-first code
-// words, stop flags into bytes of the 32-position mask words.
-template <int BITS, int TILE, int T>
-__device__ __forceinline__ void l0_pack(const uint64_t (&r)[L0Units<BITS, TILE, T>::kPer], uint64_t *s_code,
-                                        uint32_t *s_dol, const uint8_t *lut4, int acgt_only, bool packed) {
-    using U = L0Units<BITS, TILE, T>;
-    using P = L0Pack<BITS, TILE>;
-    constexpr uint64_t kOnes = 0x0101010101010101ull;
-    if (BITS == 2 && packed) {
-#pragma unroll
-        for (int j = 0; j < U::kPer / 2; ++j) {
-            const uint32_t g = threadIdx.x + j * T;
-            if (g < (uint32_t)P::kGroups) {
-                s_code[g] = r[2 * j];
-                s_dol[g] = (uint32_t)r[2 * j + 1];
-            }
-        }
-        if (threadIdx.x == 0) s_code[P::kCodeWords - 1] = 0;
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < U::kPer; ++j) {
-        const uint32_t u = threadIdx.x + j * T;
-        if (u < (uint32_t)U::kUnits) {
-            const uint64_t x = r[j];
-            uint64_t z;
-            if (acgt_only)
-                z = non_acgt_bytes(x);
-            else
-                z = zero_bytes(x ^ (kOnes * GK_DOLLAR));
-            reinterpret_cast<uint8_t *>(s_dol)[(u & ~3u) + 3 - (u & 3u)] = (uint8_t)gather_flags8(z);
-            if (BITS == 2) {
-                reinterpret_cast<uint16_t *>(s_code)[(u & ~3u) + 3 - (u & 3u)] = (uint16_t)pack2_8(x);
-            } else {
-                uint32_t v = 0;
-#pragma unroll
-                for (int b = 0; b < 8; ++b) v = (v << 4) | lut4[(x >> (8 * b)) & 0xFFu];
-                reinterpret_cast<uint32_t *>(s_code)[(u & ~1u) + 1 - (u & 1u)] = v;
-            }
-        }
-    }
-    if (threadIdx.x == 0) s_code[P::kCodeWords - 1] = 0;
-}
-
-template <int BITS>
-__device__ __forceinline__ uint64_t l0_key(const uint64_t *s_code, uint32_t p, int B) {
-    const uint32_t o = p * BITS, w = o >> 6, s = o & 63;
-    uint64_t x = s_code[w] << s;
-    if (s) x |= s_code[w + 1] >> (64 - s);
-    return x >> (64 - B);
-}
-
-// CANON: the first key word of the canonical k-mer (gkm_canon.h) is the smaller of the first word
-// of the k-mer and the first word of its reverse complement -- the reverse complement of the
-// k-mer's last B / BITS symbols.  (If the two are equal the whole-k-mer choice does not change the
-// first word; later words are decided in tie_encode_kernel.)
-template <int BITS, bool CANON>
-__device__ __forceinline__ uint64_t l0_key_of(const uint64_t *s_code, uint32_t p, int B, int k) {
-    const uint64_t f = l0_key<BITS>(s_code, p, B);
-    if (!CANON) return f;
-    const int n = B / BITS;
-    const uint64_t r = revcomp_word<BITS>(l0_key<BITS>(s_code, p + k - n, B), n);
-    return r < f ? r : f;
-}
-
-__device__ __forceinline__ bool l0_valid(const uint32_t *s_dol, uint32_t p, int S) {
-    const uint32_t w = p >> 5, s = p & 31;
-    const uint64_t x = (((uint64_t)s_dol[w] << 32) | s_dol[w + 1]) << s;
-    if (S <= 32) return (x >> (64 - S)) == 0;
-    // multi-word keys (33 <= S <= 64): the first 32 positions, then the rest from p + 32
-    const uint64_t y = (((uint64_t)s_dol[w + 1] << 32) | s_dol[w + 2]) << s;
-    return (x >> 32) == 0 && (y >> (96 - S)) == 0;
-}
-
-// Eight consecutive positions q0 .. q0 + 7 (q0 % 8 == 0) of a packed 2-bit tile from one 128-bit
-// code window and one 64-position stop window: keep mask (valid, before a.hi, owned) and the keys
-// (only if `keys`) or the L0 digits.  When no lane of the wave sees a stop or the sequence end and
-// the L0 digit is the top 7 bits of a key of >= 8 bits, the digits come straight from the window's
-// high half (bits [25 - 2i, 32 - 2i)) -- a shift, a mask and a compare per position.
-struct Win8 {
-    uint64_t T, T2;  // symbols q0 .., q0 + 32 ..
-    uint64_t D;      // stops q0 .. q0 + 63, MSB first
-};
-
-__device__ __forceinline__ Win8 win8_load(const uint64_t *s_code, const uint32_t *s_dol, uint32_t q0) {
-    const uint32_t w0 = q0 >> 5, s0 = (q0 & 31) * 2;  // s0 in {0, 16, 32, 48}
-    const uint64_t A0 = s_code[w0], A1 = s_code[w0 + 1], A2 = s_code[w0 + 2];
-    Win8 w;
-    w.T = s0 ? (A0 << s0) | (A1 >> (64 - s0)) : A0;
-    w.T2 = s0 ? (A1 << s0) | (A2 >> (64 - s0)) : A1;
-    const uint32_t ds = q0 & 31;  // in {0, 8, 16, 24}
-    const uint64_t D0 = ((uint64_t)s_dol[w0] << 32) | s_dol[w0 + 1];
-    w.D = ds ? (D0 << ds) | (s_dol[w0 + 2] >> (32 - ds)) : D0;
-    return w;
-}
-
-__device__ __forceinline__ uint64_t win8_key(const Win8 &w, int i, int B) {
-    const uint64_t Ti = i ? (w.T << (2 * i)) | (w.T2 >> (64 - 2 * i)) : w.T;
-    return B >= 64 ? Ti : Ti >> (64 - B);
-}
-
-// the 32 symbols from position q of a packed 2-bit tile, MSB first (any q)
-__device__ __forceinline__ uint64_t win32_at(const uint64_t *s_code, uint32_t q) {
-    const uint32_t w = q >> 5, s = (q & 31) * 2;
-    return s ? (s_code[w] << s) | (s_code[w + 1] >> (64 - s)) : s_code[w];
-}
-
-// wave-uniform call (a ballot inside)
-__device__ __forceinline__ uint32_t win8_keep(const Win8 &w, const L0Args &a, Dig d0, int64_t left,
-                                              const uint32_t *s_dol, uint32_t q0, uint32_t (&dig)[8]) {
-    const uint32_t Th = (uint32_t)(w.T >> 32);
-    const bool top7 = d0.mask == 0x7Fu && (int)d0.shift == a.total_bits - 7 && a.symbols <= 56;
-    uint32_t keepm = 0;
-    // ownership digits of up to 18 bits come from the same 32-bit window (2 i + own_bits <= 32)
-    const uint32_t omask = (1u << a.own_bits) - 1;
-    if (top7 && a.own_bits <= a.total_bits && a.own_bits <= 18 && __ballot(w.D != 0 || left < 8) == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            dig[i] = (Th >> (25 - 2 * i)) & 0x7Fu;
-            keepm |= (l0_owned((Th >> (32 - 2 * i - a.own_bits)) & omask, a) ? 1u : 0u) << i;
-        }
-        return keepm;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint64_t key = win8_key(w, i, a.total_bits);
-        dig[i] = dg_of(key, d0);
-        const uint64_t Di = w.D << i;
-        const bool valid = a.symbols <= 56 ? (Di == 0 || (int)__clzll((long long)Di) >= a.symbols)
-                                           : l0_valid(s_dol, q0 + i, a.symbols);
-        keepm |= ((valid && i < left && l0_owned_key(key, a)) ? 1u : 0u) << i;
-    }
-    return keepm;
-}
-
-template <int BITS, int T, int I, int R, bool CANON = false>
-__global__ __launch_bounds__(T) void msd0_count_kernel(L0Args a, Dig d0, uint32_t *__restrict__ tile_hist,
-                                                       uint32_t ntiles) {
-    constexpr int TILE = T * I;
-    constexpr int RADIX = 1 << R;
-    using P = L0Pack<BITS, TILE>;
-    __shared__ uint64_t s_code[P::kCodeWords];
-    __shared__ uint32_t s_dol[P::kGroups];
-    // 4 interleaved histogram copies (digit d, copy c at 4 d + c; copy = thread & 3): the lanes of
-    // one atomic that share a digit land on 4 different words in 4 banks (C3: 1.845 -> 1.797 ms, A/B)
-    constexpr int NC = 4;
-    __shared__ uint32_t s_hist[RADIX * NC];
-    __shared__ uint8_t s_lut4[256];
-    const int t = threadIdx.x;
-    if (t < 256) s_lut4[t] = c_code4_msd[t];
-    // persistent: the next tile's bytes are loaded while this one is counted
-    uint64_t rr[L0Units<BITS, TILE, T>::kPer];
-    if (blockIdx.x < ntiles) l0_load<BITS, TILE, T>(a, a.lo + (uint64_t)blockIdx.x * TILE, rr);
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t P0 = a.lo + (uint64_t)tile * TILE;
-        // each thread zeroes the copies it summed for the previous tile (no barrier between)
-        for (int i = t; i < RADIX; i += T)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) s_hist[i * NC + c] = 0;
-        lds_barrier();  // the LUT; the previous tile's histogram and codes have been read
-        l0_pack<BITS, TILE, T>(rr, s_code, s_dol, s_lut4, a.acgt_only, a.pk_code != nullptr);
-        lds_barrier();
-        if (tile + gridDim.x < ntiles) l0_load<BITS, TILE, T>(a, P0 + (uint64_t)gridDim.x * TILE, rr);
-        if constexpr (BITS == 2 && !CANON) {  // 8 consecutive positions per thread (Win8)
-            static_assert(TILE % 8 == 0 && (TILE / 8) % 64 == 0, "whole waves per round");
-            for (uint32_t g = t; g < TILE / 8; g += T) {
-                const uint32_t q0 = g * 8;
-                const Win8 w = win8_load(s_code, s_dol, q0);
-                uint32_t dig[8];
-                const uint32_t keepm = win8_keep(w, a, d0, (int64_t)a.hi - (int64_t)(P0 + q0), s_dol, q0, dig);
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if ((keepm >> i) & 1u) atomicAdd(&s_hist[dig[i] * NC + (t & (NC - 1))], 1u);
-            }
-        } else {
-            // canonical 2-bit keys in a tile without stops: the digit is the smaller of the forward
-            // and the reverse-complement top 7 bits, 8 consecutive positions per thread from two
-            // 32-symbol windows (at q0 and at q0 + k - 4)
-            bool fast = false;
-            if constexpr (BITS == 2 && CANON && (R == 7 || R == 8)) {
-                uint32_t anystop = 0;
-                for (int j = t; j < P::kGroups; j += T) anystop |= s_dol[j];
-                // (ownership digits other than the L0 digit -- the key-range ranks' 12 bits -- take the
-                // per-position path below)
-                fast = __syncthreads_or(anystop != 0) == 0 && P0 + TILE <= a.hi &&
-                       (d0.mask == 0x7Fu || d0.mask == 0xFFu) && (int)d0.shift == a.total_bits - R &&
-                       a.symbols >= 4 && (a.own_span == 0xFFFFFFFFu || a.own_bits == R);
-                if (fast) {
-                    for (uint32_t g = t; g < TILE / 8; g += T) {
-                        const uint32_t q0 = g * 8;
-                        // only the top 32 bits of each window are read (16 symbols: positions q0 .. q0 + 10,
-                        // q0 + k - 4 .. q0 + k + 6): 32-bit shifts per position instead of 64-bit ones
-                        // (the 64-bit form ran this pass VALU-bound at 5.0 ms for C5)
-                        const uint32_t tf = (uint32_t)(win32_at(s_code, q0) >> 32);
-                        const uint32_t tr = (uint32_t)(win32_at(s_code, q0 + a.symbols - 4) >> 32);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            // (R = 8: the top 8 bits of both words; the smaller digit is the top of the smaller word)
-                            const uint32_t f7 = (tf >> (32 - R - 2 * i)) & ((1u << R) - 1);
-                            const uint32_t v = (tr >> (24 - 2 * i)) & 0xFFu;  // symbols q0+k-4+i ..
-                            const uint32_t rv = ((v & 3u) << 6) | ((v & 0xCu) << 2) | ((v >> 2) & 0xCu) | (v >> 6);
-                            const uint32_t d = min(f7, (~rv & 0xFFu) >> (8 - R));
-                            if (l0_owned(d, a)) atomicAdd(&s_hist[d * NC], 1u);
-                        }
-                    }
-                }
-            }
-            if (!fast) {
-                // (tiles with stops, or the sequence end).  Canonical keys: two windows and a
-                // reverse complement per position -- a loop, not unrolled, so the fast path above
-                // keeps its registers (unrolled over the 96 positions it took 256 VGPRs, spilled
-                // to scratch and ran the whole kernel at one wave per SIMD).  4-bit forward keys
-                // (every tile takes this path): unrolled by 4 (fully unrolled: 256 VGPRs + 206
-                // AGPRs, one wave per SIMD)
-                constexpr int UNR = CANON ? 1 : 4;
-#pragma unroll UNR
-                for (int i = 0; i < I; ++i) {
-                    const uint32_t p = i * T + t;
-                    const uint64_t key = l0_key_of<BITS, CANON>(s_code, p, a.total_bits, a.symbols);
-                    const uint32_t d = dg_of(key, d0);
-                    if (l0_valid(s_dol, p, a.symbols) && P0 + p < a.hi && l0_owned_key(key, a))
-                        atomicAdd(&s_hist[d * NC], 1u);
-                }
-            }
-        }
-        lds_barrier();
-        for (int i = t; i < RADIX; i += T) {
-            uint32_t h = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) h += s_hist[i * NC + c];
-            tile_hist[(uint64_t)tile * RADIX + i] = h;
-        }
-    }
-}
-
-// L0 partition, software-pipelined with position staging.  The L0 input is the packed tile
-// itself, so a staged element needs only its tile position (u16): its key is re-derived from the
-// tile's codes when it is stored, and its start is the tile base + position.  Positions and codes
-// are double-buffered (2 x (48 + 6) KB at 24,576 positions), so the previous tile's stores are
-// spread over EVERY phase of this tile -- packing, ranking, scan, staging -- and the memory pipe
-// never idles (staged as (key, start) in one 135 KB buffer, the stores had to finish before the
-// staging: a phase profile showed them issued in 45 % of the tile time, backed up, and the pipe
-// idle for the rest).  Twice the tile of the level passes: runs of ~192 per digit.
-#ifndef GKM_L0_T
-#define GKM_L0_T 1024
-#endif
-#ifndef GKM_L0_I
-#define GKM_L0_I 24
-#endif
-// (tuning overrides, tools/build_variant.sh: GKM_L0_T threads x GKM_L0_I positions per tile)
-constexpr int kP0T = GKM_L0_T;           // L0 tile: kP0T threads x kP0I positions
-constexpr int kP0I = GKM_L0_I;
-constexpr int kP0Tile = kP0T * kP0I;     // 24,576 (< 65,536: positions staged as u16)
-
-// P88 (the packed L0, round 5): each element leaves as the level-1 digit byte (nd), the key bits below
-// it above the start's high bits (u64: key << shi | start >> (32 - shi)) and the start's low bits
-// (u16 in nd.out16) -- 11 B instead of 13 (key, start, digit); the level behind reads it (INP = 2)
-// OWN (the key-range ranks' fused select, round 5): only k-mers whose ownership digit (the top
-// a.own_bits key bits) is in the rank's range are partitioned -- the select pass and its 13-byte
-// round trip per kept k-mer fall away
-template <int BITS, int T, int I, int R, bool ND, bool CANON = false, bool P88 = false, bool OWN = false>
-__global__ __launch_bounds__(T) void msd0_pipe_kernel(L0Args a, Dig d0, const uint32_t *__restrict__ tile_off,
-                                                      uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
-                                                      uint32_t ntiles, uint64_t sink, NextDigits nd) {
-    constexpr int TILE = T * I;
-    static_assert(TILE < 65536, "tile positions are staged as u16");
-    constexpr int RADIX = 1 << R;
-    constexpr int NW = T / 64;
-    // store groups of the previous tile: G_TOP after the packing, one per ranked item, G_SCAN
-    // during the scan, the rest after the staging
-#ifndef GKM_L0_GTOP
-#define GKM_L0_GTOP 1
-#endif
-#ifndef GKM_L0_GSCAN
-#define GKM_L0_GSCAN 2
-#endif
-    // (tuning overrides, tools/gpu_ab_l0_groups.sh: G_TOP 1 beat 0, 2 and 4 by 0.2-0.6 ms at C3)
-    constexpr int G_TOP = GKM_L0_GTOP, G_SCAN = GKM_L0_GSCAN;
-    constexpr int G_RANK = I - G_TOP - G_SCAN - 2 > 0 ? I - G_TOP - G_SCAN - 2 : 0;
-    using P = L0Pack<BITS, TILE>;
-    static_assert(T >= RADIX, "one thread per digit");
-    __shared__ uint16_t s_pos[2][TILE + 2];          // positions in digit order (slot TILE: sink)
-    __shared__ uint64_t s_code[2][P::kCodeWords];   // this tile's and the staged tile's codes
-    __shared__ uint32_t s_dol[P::kGroups];
-    __shared__ uint32_t s_wc[NW * RADIX];
-    __shared__ uint32_t s_toff[2][RADIX];
-    __shared__ uint32_t s_start[RADIX + 1];
-    __shared__ uint32_t s_wsum[RADIX / 64 > 0 ? RADIX / 64 : 1];
-    __shared__ uint8_t s_lut4[256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 256) s_lut4[tid] = c_code4_msd[tid];
-    // the first iteration's stores read buffer 1 before anything was staged (they go to the
-    // sink): keep their positions inside the tile
-    for (int i = tid; i < TILE + 2; i += T) s_pos[1][i] = 0;
-    lds_barrier();  // the LUT, read by every thread's pack
-    const TileWalk walk(ntiles);
-    uint64_t rr[L0Units<BITS, TILE, T>::kPer];
-    uint32_t toff = 0;
-    auto load = [&](uint32_t t) {
-        toff = tile_off[(uint64_t)t * RADIX + (tid & (RADIX - 1))];
-        l0_load<BITS, TILE, T>(a, a.lo + (uint64_t)t * TILE, rr);
-    };
-    uint32_t pcnt = 0;  // staged elements of the previous tile (0: none -> its stores go to the sink)
-    uint64_t pP0 = 0;   // the previous tile's first position
-    int b = 0;          // this tile's buffers; b ^ 1: the staged previous tile
-    // one store group of the previous tile: slot s -> position -> key (from the staged codes)
-    auto store_group = [&](int g) {
-        const uint32_t s = min((uint32_t)(tid + g * T), pcnt - 1);  // pcnt == 0: stays in the tile
-        const uint32_t p = s_pos[b ^ 1][s];
-        const uint64_t key = l0_key_of<BITS, CANON>(s_code[b ^ 1], p, a.total_bits, a.symbols);
-        const uint64_t o = pcnt ? (uint64_t)(s_toff[b ^ 1][dg_of(key, d0)] + s) : sink;
-        if (P88) {
-            const uint32_t st = (uint32_t)(pP0 + p);
-            const int shi = nd.pshi;
-            kout[o] = (key << shi) | (st >> (32 - shi));  // (the sorted and digit bits shift out)
-            nd.out16[o] = (uint16_t)(st & ((1u << (32 - shi)) - 1));
-            nd.out[o] = (uint8_t)dg_of(key, nd.d);
-        } else {
-            if (kout) kout[o] = key;  // (none: a starts-only shard send, GK_SHARD_STARTS_ONLY)
-            vout[o] = (uint32_t)(pP0 + p);
-            if (ND) nd.out[o] = (uint8_t)dg_of(key, nd.d);
-        }
-        // keep each group's loads and stores in place: hoisting the groups' LDS reads ahead (the
-        // scheduler's choice) keeps 22 groups' positions and keys live and spills them to scratch,
-        // whose vmcnt waits then drain every store in flight
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    if (walk.first < walk.end) load(walk.first);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (uint32_t t = walk.first; t < walk.end; t += walk.step) {
-        uint32_t *wc = s_wc + wave * RADIX;
-#pragma unroll
-        for (int u = 0; u < (RADIX + 63) / 64; ++u)
-            if (u * 64 + lane < RADIX) wc[u * 64 + lane] = 0;
-        if (tid < RADIX) s_toff[b][tid] = toff;
-        l0_pack<BITS, TILE, T>(rr, s_code[b], s_dol, s_lut4, a.acgt_only, a.pk_code != nullptr);
-        // rr and toff are consumed: the next tile's bytes fly during this whole tile (the last
-        // tile re-loads itself, so every iteration issues the same loads: static wait counts)
-        load(min(t + walk.step, walk.end - 1));
-#pragma unroll
-        for (int g = 0; g < G_TOP; ++g) store_group(g);
-        lds_barrier();  // packed codes visible
-        const uint64_t P0 = a.lo + (uint64_t)t * TILE;
-        // a tile without stops that ends before a.hi: every position starts a k-mer (wave-uniform)
-        uint32_t anystop = 0;
-#pragma unroll
-        for (int j = 0; j < (P::kGroups + 63) / 64; ++j)
-            anystop |= s_dol[min((uint32_t)(j * 64 + lane), (uint32_t)P::kGroups - 1)];
-        const bool clean = __ballot(anystop != 0) == 0 && P0 + TILE <= a.hi;
-        uint32_t dr[I], validm = 0;  // per item: digit | rank << 8 (rank < I * 64)
-        uint32_t p0 = wave * (I * 64) + lane;
-        asm volatile("" : "+v"(p0));
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint32_t p = p0 + i * 64;
-            const uint64_t key = l0_key_of<BITS, CANON>(s_code[b], p, a.total_bits, a.symbols);
-            bool valid = clean || (l0_valid(s_dol, p, a.symbols) && P0 + p < a.hi);
-            if (OWN) valid = valid && l0_owned_key(key, a);
-            validm |= (valid ? 1u : 0u) << i;
-            const uint32_t dig = dg_of(key, d0);
-            // stable rank by one returning LDS atomic (rank_atomic, gkm_partition.h); the LDS-mask
-            // round trip it replaces took C3 L0 14.0 -> 12.9 ms against R + 1 ballots per item
-            dr[i] = dig | (rank_atomic(wc, dig, valid) << 8);
-            if (i < G_RANK) store_group(G_TOP + i);
-            __builtin_amdgcn_sched_barrier(0);  // one item at a time (register pressure, see above)
-        }
-        lds_barrier();  // ranks final
-        uint32_t total = 0, incl = 0;
-        if (tid < RADIX) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const uint32_t v = s_wc[w * RADIX + tid];
-                s_wc[w * RADIX + tid] = total;
-                total += v;
-            }
-            incl = wave_incl_scan(total);
-            if (lane == 63) s_wsum[wave] = incl;
-        }
-#pragma unroll
-        for (int g = 0; g < G_SCAN; ++g) store_group(G_TOP + G_RANK + g);
-        lds_barrier();
-        if (tid < RADIX) {
-            uint32_t pre = 0;
-            for (int w = 0; w < wave; ++w) pre += s_wsum[w];
-            const uint32_t st = pre + incl - total;
-            s_start[tid] = st;
-            s_toff[b][tid] -= st;
-            if (tid == RADIX - 1) s_start[RADIX] = pre + incl;
-        }
-        lds_barrier();
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const bool valid = (validm >> i) & 1u;
-            const uint32_t dg = dr[i] & 0xFFu;
-            const uint32_t sl = valid ? s_start[dg] + wc[dg] + (dr[i] >> 8) : (uint32_t)TILE;
-            s_pos[b][sl] = (uint16_t)(p0 + i * 64);
-        }
-        const uint32_t cnt = s_start[RADIX];
-#pragma unroll
-        for (int g = G_TOP + G_RANK + G_SCAN; g < I; ++g) store_group(g);
-        pcnt = cnt;
-        pP0 = P0;
-        lds_barrier();  // staging complete; counters, codes and the previous staging read
-        b ^= 1;
-    }
-    if (walk.first < walk.end) {
-#pragma unroll
-        for (int g = 0; g < I; ++g) store_group(g);
-    }
-}
-
-// Wide L0 partition (R = 10 or 11 bits; 2-bit keys of one word, forward): the
-// position-staged, software-pipelined scheme of msd0_pipe_kernel with a digit space the 7-bit one
-// cannot hold -- per-wave u16 counters, two per word (rank_atomic16), K = RADIX / T digits per
-// thread in the scan, K tile offsets per thread.  With the level pass behind it, 11 + 8 bits leave
-// the C3 buckets at ~5.9 K keys, finished in one block-local round (three passes instead of
-// four global ones plus the wave-local round).
-template <int T, int I, int R, bool ND>
-__global__ __launch_bounds__(T) void msd0_wide_kernel(L0Args a, Dig d0, const uint32_t *__restrict__ tile_off,
-                                                      uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
-                                                      uint32_t ntiles, uint64_t sink, NextDigits nd) {
-    constexpr int TILE = T * I;
-    static_assert(TILE < 65536, "tile positions are staged as u16");
-    constexpr int RADIX = 1 << R;
-    constexpr int NW = T / 64;
-    constexpr int K = RADIX / T;  // digits per thread in the scan
-    static_assert(RADIX % T == 0 && K >= 1, "whole digits per thread");
-    static_assert(I * 64 < 65536, "per-wave counts fit 16 bits");
-    constexpr int G_TOP = 1, G_SCAN = 2;
-    constexpr int G_RANK = I - G_TOP - G_SCAN - 2 > 0 ? I - G_TOP - G_SCAN - 2 : 0;
-    using P = L0Pack<2, TILE>;
-    __shared__ uint16_t s_pos[2][TILE + 2];          // positions in digit order (slot TILE: sink)
-    __shared__ uint64_t s_code[2][P::kCodeWords];   // this tile's and the staged tile's codes
-    __shared__ uint32_t s_dol[P::kGroups];
-    __shared__ uint32_t s_wc[NW * RADIX / 2];        // per-wave u16 digit counters
-    __shared__ uint32_t s_toff[2][RADIX];
-    __shared__ uint32_t s_start[RADIX + 1];
-    __shared__ uint32_t s_wsum[NW];
-    uint16_t *const s_wc16 = reinterpret_cast<uint16_t *>(s_wc);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < TILE + 2; i += T) s_pos[1][i] = 0;
-    lds_barrier();
-    const TileWalk walk(ntiles);
-    uint64_t rr[L0Units<2, TILE, T>::kPer];
-    uint32_t toff[K];
-    auto load = [&](uint32_t t) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) toff[k] = tile_off[(uint64_t)t * RADIX + tid * K + k];
-        l0_load<2, TILE, T>(a, a.lo + (uint64_t)t * TILE, rr);
-    };
-    uint32_t pcnt = 0;
-    uint64_t pP0 = 0;
-    int b = 0;
-    auto store_group = [&](int g) {
-        const uint32_t s = min((uint32_t)(tid + g * T), pcnt - 1);
-        const uint32_t p = s_pos[b ^ 1][s];
-        const uint64_t key = l0_key<2>(s_code[b ^ 1], p, a.total_bits);
-        const uint64_t o = pcnt ? (uint64_t)(s_toff[b ^ 1][dg_of(key, d0)] + s) : sink;
-        kout[o] = key;
-        vout[o] = (uint32_t)(pP0 + p);
-        if (ND) nd.out[o] = (uint8_t)dg_of(key, nd.d);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    if (walk.first < walk.end) load(walk.first);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (uint32_t t = walk.first; t < walk.end; t += walk.step) {
-        uint32_t *wc = s_wc + wave * (RADIX / 2);
-#pragma unroll
-        for (int u = 0; u < RADIX / 2 / 64; ++u) wc[u * 64 + lane] = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) s_toff[b][tid * K + k] = toff[k];
-        l0_pack<2, TILE, T>(rr, s_code[b], s_dol, nullptr, 0, a.pk_code != nullptr);
-        load(min(t + walk.step, walk.end - 1));
-#pragma unroll
-        for (int g = 0; g < G_TOP; ++g) store_group(g);
-        lds_barrier();  // packed codes visible
-        const uint64_t P0 = a.lo + (uint64_t)t * TILE;
-        uint32_t anystop = 0;
-#pragma unroll
-        for (int j = 0; j < (P::kGroups + 63) / 64; ++j)
-            anystop |= s_dol[min((uint32_t)(j * 64 + lane), (uint32_t)P::kGroups - 1)];
-        const bool clean = __ballot(anystop != 0) == 0 && P0 + TILE <= a.hi;
-        uint32_t dr[I];  // per item: digit | rank << R, all ones when not valid
-        uint32_t p0 = wave * (I * 64) + lane;
-        asm volatile("" : "+v"(p0));
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint32_t p = p0 + i * 64;
-            const bool valid = clean || (l0_valid(s_dol, p, a.symbols) && P0 + p < a.hi);
-            const uint32_t dig = dg_of(l0_key<2>(s_code[b], p, a.total_bits), d0);
-            const uint32_t rk = rank_atomic16<R>(wc, dig, valid);
-            dr[i] = valid ? dig | (rk << R) : ~0u;
-            if (i < G_RANK) store_group(G_TOP + i);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier();  // ranks final
-        // per-digit totals over the waves -> per-wave exclusive prefixes (u16), block scan of the
-        // digit totals (thread tid owns digits tid K .. tid K + K - 1)
-        uint32_t tot[K], sum = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int d = tid * K + k;
-            uint32_t run = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const uint32_t v = s_wc16[w * RADIX + d];
-                s_wc16[w * RADIX + d] = (uint16_t)run;
-                run += v;
-            }
-            tot[k] = run;
-            sum += run;
-        }
-        const uint32_t incl = wave_incl_scan(sum);
-        if (lane == 63) s_wsum[wave] = incl;
-#pragma unroll
-        for (int g = 0; g < G_SCAN; ++g) store_group(G_TOP + G_RANK + g);
-        lds_barrier();
-        {
-            uint32_t pre = 0;
-            for (int w = 0; w < wave; ++w) pre += s_wsum[w];
-            uint32_t run = pre + incl - sum;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int d = tid * K + k;
-                s_start[d] = run;
-                s_toff[b][d] -= run;
-                run += tot[k];
-            }
-            if (tid == T - 1) s_start[RADIX] = run;
-        }
-        lds_barrier();
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const bool valid = dr[i] != ~0u;
-            const uint32_t dg = dr[i] & (RADIX - 1);
-            const uint32_t sl = valid ? s_start[dg] + s_wc16[wave * RADIX + dg] + (dr[i] >> R) : (uint32_t)TILE;
-            s_pos[b][sl] = (uint16_t)(p0 + i * 64);
-        }
-        const uint32_t cnt = s_start[RADIX];
-#pragma unroll
-        for (int g = G_TOP + G_RANK + G_SCAN; g < I; ++g) store_group(g);
-        pcnt = cnt;
-        pP0 = P0;
-        lds_barrier();  // staging complete; counters, codes and the previous staging read
-        b ^= 1;
-    }
-    if (walk.first < walk.end) {
-#pragma unroll
-        for (int g = 0; g < I; ++g) store_group(g);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Key-range shard select (gk_shard_sort_range)
-// ---------------------------------------------------------------------------------------------
-// A rank scans the WHOLE sequence and keeps the k-mers whose L0 digit lies in its range -- about
-// 1/N of them -- in position order.  One light streaming pass over 4096-position tiles (small LDS
-// and registers, so several workgroups per CU overlap their loads): each wave compacts its kept
-// k-mers -- the forward 2-bit keys from 8-position windows per lane, the others with one ballot per
-// row of 64 positions -- and stores them to consecutive addresses.
-// Stable: tiles, waves, rows and lanes follow positions.  The kept k-mers then go through the
-// ordinary MSD levels as one bucket (the pass writes their L0 digit bytes, so the first level
-// counts 1 byte per k-mer).  A tile is kSR rounds of 4096 positions (512 per wave per round):
-// one load of the tile's bytes (or packed words) per kSR rounds keeps more bytes in flight per
-// workgroup than one 4096-position tile did.
-#ifndef GKM_SEL_ROUNDS
-#define GKM_SEL_ROUNDS 1
-#endif
-constexpr int kST = 512, kSI = 8, kSR = GKM_SEL_ROUNDS;  // threads, rows of 64 positions per wave per round, rounds
-constexpr int kSRound = kST * kSI;                       // 4096 positions per round
-constexpr int kSTile = kSRound * kSR;                    // positions per tile
-constexpr int kSW = kST / 64;                            // waves per tile
-
-// Workgroup w walks its own chunk of tpw consecutive tiles and appends its kept k-mers at a running
-// offset into its own region of the output, [t0 * kSTile, (t0 + tpw) * kSTile) (room for every
-// position of the chunk, so no count pass is needed); wave_cnt[w] receives the chunk's kept count.
-// The regions, in workgroup order, are the pieces of one bucket in position order
-// (first_level_from_pieces).
-template <int BITS, bool CANON>
-#ifndef GKM_SEL_MINW
-#define GKM_SEL_MINW 1
-#endif
-// (tuning override: GKM_SEL_MINW = the waves per SIMD the forward kernels' registers are capped
-// for; the canonical ones would spill to scratch)
-__global__ __launch_bounds__(kST, CANON ? 1 : GKM_SEL_MINW) void msd0_select_kernel(L0Args a, Dig d0, uint32_t ntiles, uint32_t tpw,
-                                                          uint32_t *__restrict__ wave_cnt,
-                                                          uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
-                                                          uint8_t *__restrict__ nd_out) {
-    using P = L0Pack<BITS, kSTile>;
-    // per-wave staging of the kept positions (tile-relative u16; the key is re-derived from the
-    // tile's codes when it is stored): 512 slots + one dump slot per lane for the positions not
-    // kept, so the staging writes need no branch.  (Staged as (key, start), 48 KB, the kernel fit
-    // 3 workgroups per CU and its divergent staging loop cost more scalar than vector work.)
-    constexpr int kSlots = 512 + 64;
-    constexpr int kStage = kSW * kSlots;
-    __shared__ uint64_t s_code[P::kCodeWords];
-    __shared__ uint32_t s_dol[P::kGroups];
-    __shared__ uint8_t s_lut4[256];
-    __shared__ uint16_t s_spos[kStage];
-    __shared__ uint32_t s_wtot[2][kSW];  // per round parity (a round's barrier orders the reuse)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 256) s_lut4[tid] = c_code4_msd[tid];
-    // tiles of this workgroup: its chunk
-    const uint32_t tfirst = blockIdx.x * tpw;
-    const uint32_t tend = min(tfirst + tpw, ntiles);
-    const uint64_t region = (uint64_t)tfirst * kSTile;  // this chunk's output region
-    uint64_t run = 0;                                   // kept so far in the chunk
-    uint64_t rr[L0Units<BITS, kSTile, kST>::kPer];
-    if (tfirst < tend) l0_load<BITS, kSTile, kST>(a, a.lo + (uint64_t)tfirst * kSTile, rr);
-    for (uint32_t t = tfirst; t < tend; ++t) {
-        const uint64_t P0 = a.lo + (uint64_t)t * kSTile;
-        __syncthreads();  // the LUT; the previous tile's codes and wave totals have been read
-        l0_pack<BITS, kSTile, kST>(rr, s_code, s_dol, s_lut4, a.acgt_only, a.pk_code != nullptr);
-        __syncthreads();
-        // the next tile's bytes fly while this one is processed
-        if (t + 1 < tend) l0_load<BITS, kSTile, kST>(a, P0 + (uint64_t)kSTile, rr);
-        // the wave's output offset from the kept counts of the tile's waves (block-uniform call)
-        auto chunk_offset = [&](uint32_t wcount, int r) -> uint64_t {
-            if (lane == 0) s_wtot[r & 1][wave] = wcount;
-            __syncthreads();
-            uint32_t pre = 0, tot = 0;
-#pragma unroll
-            for (int w = 0; w < kSW; ++w) {
-                const uint32_t v = s_wtot[r & 1][w];
-                pre += w < wave ? v : 0u;
-                tot += v;
-            }
-            const uint64_t o = region + run + pre;
-            run += tot;
-            return o;
-        };
-        for (int r = 0; r < kSR; ++r) {
-            const uint32_t R0 = r * kSRound;                       // the round's first tile position
-            // forward 2-bit keys: 8 consecutive positions per thread (Win8).  Canonical keys keep the
-            // row layout below (a per-lane loop over the kept positions' canonical keys was slower:
-            // 11.9 against 8.3 ms per C5 rank at N = 8)
-            if constexpr (BITS == 2 && !CANON) {
-                const uint32_t q0 = R0 + tid * 8;
-                const Win8 win8 = win8_load(s_code, s_dol, q0);
-                uint32_t dig[8];
-                const uint32_t keepm = win8_keep(win8, a, d0, (int64_t)a.hi - (int64_t)(P0 + q0), s_dol, q0, dig);
-                const uint32_t cnt = (uint32_t)__popc(keepm);
-                const uint32_t incl = wave_incl_scan(cnt);
-                const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-                const uint64_t o = chunk_offset(total, r);
-                // stage the wave's kept positions in position order, then store the k-mers as one
-                // coalesced run
-                uint16_t *sp = s_spos + wave * kSlots;
-                uint32_t j = incl - cnt;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const uint32_t kp = (keepm >> i) & 1u;
-                    sp[kp ? j : 512u + (uint32_t)lane] = (uint16_t)(q0 + i);  // (tile positions < 65,536)
-                    j += kp;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-                for (uint32_t e = lane; e < total; e += 64) {
-                    const uint32_t p = sp[e];
-                    const uint64_t k = l0_key<2>(s_code, p, a.total_bits);
-                    kout[o + e] = k;
-                    vout[o + e] = (uint32_t)(P0 + p);
-                    nd_out[o + e] = (uint8_t)dg_of(k, d0);
-                }
-            } else {
-                // one ballot per row of 64 positions
-                const uint32_t wbase = R0 + wave * (kSI * 64);
-                uint64_t key[kSI];
-                uint32_t at[kSI];
-                uint32_t keepm = 0, kept = 0;
-#pragma unroll
-                for (int i = 0; i < kSI; ++i) {
-                    const uint32_t p = wbase + i * 64 + lane;
-                    key[i] = l0_key_of<BITS, CANON>(s_code, p, a.total_bits, a.symbols);
-                    const bool keep = l0_valid(s_dol, p, a.symbols) && P0 + p < a.hi && l0_owned_key(key[i], a);
-                    const uint64_t m = __ballot(keep);
-                    at[i] = kept + lanes_below(m);
-                    kept += (uint32_t)__popcll(m);
-                    keepm |= (keep ? 1u : 0u) << i;
-                }
-                const uint64_t base = chunk_offset(kept, r);
-#pragma unroll
-                for (int i = 0; i < kSI; ++i) {
-                    if ((keepm >> i) & 1u) {
-                        const uint64_t o = base + at[i];
-                        kout[o] = key[i];
-                        vout[o] = (uint32_t)(P0 + wbase + i * 64 + lane);
-                        nd_out[o] = (uint8_t)dg_of(key[i], d0);
-                    }
-                }
-            }
-        }  // rounds
-    }
-    if (tid == 0 && blockIdx.x * tpw < ntiles) wave_cnt[blockIdx.x] = (uint32_t)run;
-}
-
-// Key-range select from the packed copy, SWAR (round 6): forward 2-bit keys of <= 32 symbols whose
-// sequence has a 2-bit packed copy (a.pk_code / a.pk_dol: 32 positions per u64 of codes and u32 of
-// stops).  No LDS tile, no barrier: each WAVE walks its own chunk of gpw consecutive 32-position
-// groups, 64 groups (2,048 positions) per step, one group per lane, and appends its kept k-mers at
-// a running offset into its own region of the output, [first group * 32, + gpw * 32) -- the pieces
-// of one bucket in position order, as the workgroup chunks of msd0_select_kernel are.
-// Per lane and group (w = the group's codes, x2 = the top half of the next group's codes):
-//   ownership digit of position j = the top own_bits bits of the 32-bit window at bit 2 j of
-//   w:x2 (one funnel shift); the range test is one subtract and one compare against the range
-//   shifted to the window's top, so the digit is never extracted (~4 VALU per position; the tile
-//   select spent ~20 per position, VALU-bound at 2.8 ms per C3 rank);
-//   stops: a lane with a stop in its 64-position window smears them over S positions in 5
-//   doubling steps (all 32 positions at once).
-// The kept positions are staged per wave as group-relative u16 in position order (a loop over the
-// set bits of the keep mask), the step's 65 code words beside them, and the k-mers leave as one
-// coalesced run: key (re-derived from the staged words), start, L0 digit byte.
-constexpr int kRselW = 4;  // waves per workgroup (independent: no barrier)
-__global__ __launch_bounds__(kRselW * 64) void msd0_rsel_kernel(L0Args a, Dig d0, uint64_t ngroups, uint64_t gpw,
-                                                                 uint32_t lo_w, uint32_t spm1_w,
-                                                                 uint32_t *__restrict__ wave_cnt,
-                                                                 uint64_t *__restrict__ kout,
-                                                                 uint32_t *__restrict__ vout,
-                                                                 uint8_t *__restrict__ nd_out) {
-    __shared__ uint16_t s_pos[kRselW][2048];
-    __shared__ uint64_t s_w[kRselW][65];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t gw = (uint64_t)blockIdx.x * kRselW + wave;
-    const uint64_t g0 = gw * gpw, g1 = min(g0 + gpw, ngroups);
-    uint16_t *sp = s_pos[wave];
-    uint64_t *sw = s_w[wave];
-    const int S = a.symbols, B = a.total_bits;
-    uint64_t run = 0;
-    const uint64_t out0 = g0 * 32;
-    // software pipeline: the next step's words fly while this one is processed
-    uint64_t w = 0, w1 = 0;
-    uint32_t d = 0, d1 = 0;
-    auto load = [&](uint64_t base) {
-        const uint64_t g = min(base + (uint64_t)lane, ngroups - 1);
-        w = a.pk_code[g];
-        w1 = a.pk_code[g + 1];
-        d = a.pk_dol[g];
-        d1 = a.pk_dol[g + 1];
-    };
-    if (g0 < g1) load(g0);
-    for (uint64_t base = g0; base < g1; base += 64) {
-        const uint64_t W0 = w, W1 = w1;
-        const uint32_t D0 = d, D1 = d1;
-        const bool live = base + (uint64_t)lane < g1;
-        if (base + 64 < g1) load(base + 64);
-        // ownership: position j <-> bit 31 - j of m (MSB first, the order of the staging loop)
-        const uint32_t x0 = (uint32_t)(W0 >> 32), x1 = (uint32_t)W0, x2 = (uint32_t)(W1 >> 32);
-        uint32_t m = 0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int r = (2 * j) & 31;
-            const uint32_t hi = j < 16 ? x0 : x1, lo = j < 16 ? x1 : x2;
-            const uint32_t win = r ? __builtin_amdgcn_alignbit(hi, lo, 32 - r) : hi;
-            m = (m << 1) | (uint32_t)(win - lo_w <= spm1_w);
-        }
-        // stops: invalid where a stop lies in [j, j + S); D0 / D1 bit 31 - i = position i
-        if (__ballot((D0 | D1) != 0)) {
-            uint64_t x = ((uint64_t)D0 << 32) | D1;
-            uint64_t sm = x;  // sm: a stop in [j, j + len)
-            int len = 1;
-#pragma unroll
-            for (int s = 1; s < 32; s <<= 1) {
-                if (2 * len <= S) {
-                    sm |= sm << len;
-                    len *= 2;
-                }
-            }
-            if (len < S) sm |= sm << (S - len);
-            m &= ~(uint32_t)(sm >> 32);
-        }
-        if (!live) m = 0;
-        const uint32_t cnt = (uint32_t)__popc(m);
-        const uint32_t incl = wave_incl_scan(cnt);
-        const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-        if (total == 0) continue;
-        // stage: the group-relative positions of the kept k-mers in position order, the words
-        uint32_t j = incl - cnt;
-        while (m) {
-            const uint32_t b = __clz(m);
-            sp[j++] = (uint16_t)(lane * 32 + b);
-            m ^= 0x80000000u >> b;
-        }
-        sw[lane] = W0;
-        if (lane == 63) sw[64] = W1;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-        const uint64_t o = out0 + run, P0 = base * 32;
-        for (uint32_t e = lane; e < total; e += 64) {
-            const uint32_t p = sp[e], q = p >> 5, s = (p & 31) * 2;
-            const uint64_t A = sw[q];
-            const uint64_t T = s ? (A << s) | (sw[q + 1] >> (64 - s)) : A;
-            const uint64_t k = T >> (64 - B);
-            kout[o + e] = k;
-            vout[o + e] = (uint32_t)(P0 + p);
-            nd_out[o + e] = (uint8_t)dg_of(k, d0);
-        }
-        run += total;
-        // the next step's staging overwrites these slots: every lane has read them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    }
-    if (lane == 0 && g0 < ngroups) wave_cnt[gw] = (uint32_t)run;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Key-range ranks' L0, compaction first (round 6): the fused select of msd0_pipe_kernel<..., OWN>
-// ranked, staged and keyed EVERY position of the sequence to store the ~1/N it keeps (7.7 ms over
-// C3 at any N).  These two kernels test the positions with the SWAR range test of msd0_rsel_kernel
-// (forward 2-bit keys of <= 32 symbols, packed copy), compact the kept ones per tile in position
-// order, and only then rank, stage and store them -- the L0 partition of the rank's k-mers
-// straight from the sequence: no select pass, no 13-byte round trip, no level from pieces.
-// Tiles are the L0's (kP0Tile = 768 groups of 32 positions, l0_count's tables); threads < 768
-// take one group each in the test, the kept elements then spread over all 1,024 threads in the
-// partition's wave-major item order (stable: items of a wave in order, waves in order).
-// ---------------------------------------------------------------------------------------------
-constexpr int kOwnT = 1024, kOwnG = kP0Tile / 32;  // threads, groups per tile
-constexpr int kOwnI = kP0Tile / kOwnT;             // items per thread (capacity: every position)
-static_assert(kOwnG <= kOwnT && kOwnI * kOwnT == kP0Tile, "one group per thread; every position fits");
-
-struct OwnTest {
-    uint32_t lo_w, spm1_w;  // the range shifted to the top of a 32-bit window (msd0_rsel_kernel)
-};
-
-// keep mask of the group at position P (bit 31 - j = position P + j): in [a.lo, a.hi), no stop in
-// [j, j + S), ownership digit in range; W0 / W1 / D0 / D1 the group's and the next group's words.
-// Wave-uniform call (a ballot inside).
-__device__ __forceinline__ uint32_t own_keep(const L0Args &a, OwnTest ot, uint64_t P, uint64_t W0, uint64_t W1,
-                                             uint32_t D0, uint32_t D1, bool live) {
-    const uint32_t x0 = (uint32_t)(W0 >> 32), x1 = (uint32_t)W0, x2 = (uint32_t)(W1 >> 32);
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int r = (2 * j) & 31;
-        const uint32_t hi = j < 16 ? x0 : x1, lo = j < 16 ? x1 : x2;
-        const uint32_t win = r ? __builtin_amdgcn_alignbit(hi, lo, 32 - r) : hi;
-        m = (m << 1) | (uint32_t)(win - ot.lo_w <= ot.spm1_w);
-    }
-    if (__ballot(live && (D0 | D1) != 0)) {
-        uint64_t sm = ((uint64_t)D0 << 32) | D1;
-        int len = 1;
-#pragma unroll
-        for (int s = 1; s < 32; s <<= 1) {
-            if (2 * len <= a.symbols) {
-                sm |= sm << len;
-                len *= 2;
-            }
-        }
-        if (len < a.symbols) sm |= sm << (a.symbols - len);
-        m &= ~(uint32_t)(sm >> 32);
-    }
-    const uint64_t jb = a.lo > P ? a.lo - P : 0, je = a.hi > P ? min(a.hi - P, (uint64_t)32) : 0;
-    m &= jb < je ? (uint32_t)((0xFFFFFFFFull >> jb) & ~(0xFFFFFFFFull >> je)) : 0u;
-    return live ? m : 0u;
-}
-
-// the B-bit key of position j of a group (j in [0, 32))
-__device__ __forceinline__ uint64_t group_key(uint64_t W0, uint64_t W1, uint32_t j, int B) {
-    const uint32_t s = 2 * j;
-    const uint64_t T = s ? (W0 << s) | (W1 >> (64 - s)) : W0;
-    return T >> (64 - B);
-}
-
-// count pass: per-tile histograms of the kept k-mers' L0 digits (R bits)
-template <int R>
-__global__ __launch_bounds__(kOwnT) void own_count_kernel(L0Args a, Dig d0, OwnTest ot, uint32_t *__restrict__ tile_hist,
-                                                           uint32_t ntiles) {
-    constexpr int RADIX = 1 << R, NC = 4;
-    __shared__ uint32_t s_hist[RADIX * NC];
-    const int t = threadIdx.x;
-    const uint64_t g_end = (a.hi + 31) / 32;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        for (int i = t; i < RADIX * NC; i += kOwnT) s_hist[i] = 0;
-        __syncthreads();
-        if (t < kOwnG) {
-            const uint64_t g = a.lo / 32 + (uint64_t)tile * kOwnG + t;
-            const bool live = g < g_end;
-            const uint64_t gc = live ? g : g_end - 1;
-            const uint64_t W0 = a.pk_code[gc], W1 = a.pk_code[gc + 1];
-            uint32_t m = own_keep(a, ot, gc * 32, W0, W1, a.pk_dol[gc], a.pk_dol[gc + 1], live);
-            while (m) {
-                const uint32_t j = __clz(m);
-                m ^= 0x80000000u >> j;
-                atomicAdd(&s_hist[dg_of(group_key(W0, W1, j, a.total_bits), d0) * NC + (t & (NC - 1))], 1u);
-            }
-        }
-        __syncthreads();
-        for (int i = t; i < RADIX; i += kOwnT) {
-            uint32_t h = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) h += s_hist[i * NC + c];
-            tile_hist[(uint64_t)tile * RADIX + i] = h;
-        }
-    }
-}
-
-// partition pass: the kept k-mers of each tile compacted, ranked by their L0 digit (R bits), staged
-// and stored at the tile's digit offsets -- (key, start, next digit) or the packed L0 form (P88)
-template <int R, bool P88>
-__global__ __launch_bounds__(kOwnT) void own_part_kernel(L0Args a, Dig d0, OwnTest ot,
-                                                          const uint32_t *__restrict__ tile_off,
-                                                          uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
-                                                          uint32_t ntiles, NextDigits nd) {
-    constexpr int RADIX = 1 << R, NW = kOwnT / 64;
-    __shared__ uint16_t s_pos[kP0Tile];             // kept positions in order, then in digit order
-    __shared__ uint64_t s_code[kOwnG + 1];
-    __shared__ uint32_t s_wc[NW * RADIX];
-    __shared__ uint32_t s_wsum[NW];
-    __shared__ uint32_t s_start[RADIX + 1];
-    __shared__ uint32_t s_toff[RADIX];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t g_end = (a.hi + 31) / 32;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t g0 = a.lo / 32 + (uint64_t)tile * kOwnG;
-        if (t < RADIX) s_toff[t] = tile_off[(uint64_t)tile * RADIX + t];
-        uint32_t *wc = s_wc + wave * RADIX;
-#pragma unroll
-        for (int u = 0; u < (RADIX + 63) / 64; ++u)
-            if (u * 64 + lane < RADIX) wc[u * 64 + lane] = 0;
-        // 1. test: keep mask and count of this thread's group; its code words into LDS
-        uint32_t m = 0;
-        if (t < kOwnG) {
-            const uint64_t g = g0 + t;
-            const bool live = g < g_end;
-            const uint64_t gc = live ? g : g_end - 1;
-            const uint64_t W0 = a.pk_code[gc], W1 = a.pk_code[gc + 1];
-            m = own_keep(a, ot, gc * 32, W0, W1, a.pk_dol[gc], a.pk_dol[gc + 1], live);
-            s_code[t] = W0;
-            if (t == kOwnG - 1) s_code[kOwnG] = W1;
-        }
-        const uint32_t cnt = (uint32_t)__popc(m);
-        const uint32_t incl = wave_incl_scan(cnt);
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        uint32_t pre = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const uint32_t v = s_wsum[w];
-            pre += w < wave ? v : 0u;
-            total += v;
-        }
-        // 2. compaction: the kept positions (tile-relative) in position order
-        {
-            uint32_t j = pre + incl - cnt;
-            while (m) {
-                const uint32_t b = __clz(m);
-                m ^= 0x80000000u >> b;
-                s_pos[j++] = (uint16_t)(t * 32 + b);
-            }
-        }
-        __syncthreads();
-        // 3. rank: element e = wave * kOwnI * 64 + i * 64 + lane (wave-major, position order)
-        uint32_t dr[kOwnI];
-        uint16_t pp[kOwnI];
-        const uint32_t e0 = wave * (kOwnI * 64);
-#pragma unroll
-        for (int i = 0; i < kOwnI; ++i) {
-            dr[i] = ~0u;
-            pp[i] = 0;
-            if (e0 + i * 64 < total) {  // (wave-uniform)
-                const uint32_t e = e0 + i * 64 + lane;
-                const bool valid = e < total;
-                const uint32_t p = s_pos[valid ? e : 0];
-                const uint32_t dig = dg_of(l0_key<2>(s_code, p, a.total_bits), d0);
-                const uint32_t rk = rank_atomic(wc, dig, valid);
-                dr[i] = valid ? dig | (rk << 8) : ~0u;
-                pp[i] = (uint16_t)p;
-            }
-        }
-        __syncthreads();  // ranks final; every compacted position read
-        // 4. digit starts: per-digit totals over the waves, their scan
-        uint32_t dtot = 0, dincl = 0;
-        if (t < RADIX) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const uint32_t v = s_wc[w * RADIX + t];
-                s_wc[w * RADIX + t] = dtot;
-                dtot += v;
-            }
-            dincl = wave_incl_scan(dtot);
-            if (lane == 63) s_wsum[wave] = dincl;
-        }
-        __syncthreads();
-        if (t < RADIX) {
-            uint32_t p2 = 0;
-            for (int w = 0; w < wave; ++w) p2 += s_wsum[w];
-            const uint32_t st = p2 + dincl - dtot;
-            s_start[t] = st;
-            s_toff[t] -= st;
-        }
-        __syncthreads();
-        // 5. stage in digit order (over the compacted positions: all were read in 3)
-#pragma unroll
-        for (int i = 0; i < kOwnI; ++i) {
-            if (dr[i] != ~0u) {
-                const uint32_t dg = dr[i] & 0xFFu;
-                s_pos[s_start[dg] + wc[dg] + (dr[i] >> 8)] = pp[i];
-            }
-        }
-        __syncthreads();
-        // 6. store: runs of each digit at the tile's offsets
-        const uint64_t P0 = g0 * 32;
-        for (uint32_t s = t; s < total; s += kOwnT) {
-            const uint32_t p = s_pos[s];
-            const uint64_t key = l0_key<2>(s_code, p, a.total_bits);
-            const uint64_t o = (uint64_t)s_toff[dg_of(key, d0)] + s;
-            const uint32_t st = (uint32_t)(P0 + p);
-            if (P88) {
-                const int shi = nd.pshi;
-                kout[o] = (key << shi) | (st >> (32 - shi));
-                nd.out16[o] = (uint16_t)(st & ((1u << (32 - shi)) - 1));
-            } else {
-                kout[o] = key;
-                vout[o] = st;
-            }
-            nd.out[o] = (uint8_t)dg_of(key, nd.d);
-        }
-        __syncthreads();  // the staging and the codes are read before the next tile's
-    }
-}
-
-// The same histogram from the packed copy, SWAR (round 6; forward 2-bit keys of <= 32 symbols, as
-// msd0_rsel_kernel): one 32-position group per lane, the digit of position j the top own_bits bits
-// of the 32-bit window at bit 2 j of the group's codes; positions that start no k-mer (a stop in
-// [j, j + S), or outside [lo, hi)) count into junk bins (4096 + 64 j + lane: conflict-free) instead
-// of being branched around.  One LDS table per workgroup, its waves walking the chunk together.
-__global__ __launch_bounds__(kRselW * 64) void own_hist_rsel_kernel(L0Args a, uint64_t gpb,
-                                                                     uint32_t *__restrict__ ghist) {
-    __shared__ uint32_t s_hist[4096 + 64 * 32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 4096 + 64 * 32; i += kRselW * 64) s_hist[i] = 0;
-    __syncthreads();
-    const uint64_t G0 = a.lo / 32, G1 = (a.hi + 31) / 32;
-    const uint64_t g0 = G0 + blockIdx.x * gpb, g1 = min(g0 + gpb, G1);
-    const int S = a.symbols, osh = 32 - a.own_bits;
-    for (uint64_t base = g0 + wave * 64; base < g1; base += kRselW * 64) {
-        const uint64_t g = base + lane;
-        const bool live = g < g1;
-        const uint64_t gc = live ? g : g1 - 1;
-        const uint64_t W0 = a.pk_code[gc], W1 = a.pk_code[gc + 1];
-        const uint32_t D0 = a.pk_dol[gc], D1 = a.pk_dol[gc + 1];
-        // valid positions, bit 31 - j = position j: inside [lo, hi) ...
-        const uint64_t P0 = gc * 32;
-        const uint64_t jb = a.lo > P0 ? a.lo - P0 : 0, je = a.hi - P0 < 32 ? a.hi - P0 : 32;
-        uint32_t m = live && jb < je ? (uint32_t)((0xFFFFFFFFull >> jb) & ~(0xFFFFFFFFull >> je)) : 0u;
-        // ... and no stop in [j, j + S)
-        if (__ballot((D0 | D1) != 0)) {
-            uint64_t sm = ((uint64_t)D0 << 32) | D1;
-            int len = 1;
-#pragma unroll
-            for (int s = 1; s < 32; s <<= 1) {
-                if (2 * len <= S) {
-                    sm |= sm << len;
-                    len *= 2;
-                }
-            }
-            if (len < S) sm |= sm << (S - len);
-            m &= ~(uint32_t)(sm >> 32);
-        }
-        const uint32_t x0 = (uint32_t)(W0 >> 32), x1 = (uint32_t)W0, x2 = (uint32_t)(W1 >> 32), inv = ~m;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int r = (2 * j) & 31;
-            const uint32_t hi = j < 16 ? x0 : x1, lo = j < 16 ? x1 : x2;
-            const uint32_t win = r ? __builtin_amdgcn_alignbit(hi, lo, 32 - r) : hi;
-            // (an invalid position's bin depends on the lane only: the N runs of a mixed sba would
-            // otherwise send a whole wave to one address, serialising the atomic)
-            const uint32_t bin = ((inv >> (31 - j)) & 1u) ? 4096u + 64u * j + (uint32_t)lane : win >> osh;
-            atomicAdd(&s_hist[bin], 1u);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < (1 << a.own_bits); i += kRselW * 64)
-        if (s_hist[i]) atomicAdd(&ghist[i], s_hist[i]);
-}
-
-// Ownership-digit histogram of a key-range shard's position share: the top own_bits (<= 12) bits
-// of every k-mer starting in [a.lo, a.hi), one LDS table per workgroup flushed into ghist.
-template <int BITS, bool CANON>
-__global__ __launch_bounds__(kST) void own_hist_kernel(L0Args a, uint32_t ntiles, uint32_t *__restrict__ ghist) {
-    using P = L0Pack<BITS, kSTile>;
-    __shared__ uint64_t s_code[P::kCodeWords];
-    __shared__ uint32_t s_dol[P::kGroups];
-    __shared__ uint8_t s_lut4[256];
-    __shared__ uint32_t s_hist[4096];
-    const int tid = threadIdx.x;
-    if (tid < 256) s_lut4[tid] = c_code4_msd[tid];
-    for (int i = tid; i < 4096; i += kST) s_hist[i] = 0;
-    const int osh = a.total_bits - a.own_bits;
-    uint64_t rr[L0Units<BITS, kSTile, kST>::kPer];
-    if (blockIdx.x < ntiles) l0_load<BITS, kSTile, kST>(a, a.lo + (uint64_t)blockIdx.x * kSTile, rr);
-    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t P0 = a.lo + (uint64_t)t * kSTile;
-        __syncthreads();  // the LUT and the zeroed table; the previous tile's codes have been read
-        l0_pack<BITS, kSTile, kST>(rr, s_code, s_dol, s_lut4, a.acgt_only, a.pk_code != nullptr);
-        __syncthreads();
-        if (t + gridDim.x < ntiles) l0_load<BITS, kSTile, kST>(a, P0 + (uint64_t)gridDim.x * kSTile, rr);
-#pragma unroll
-        for (int i = 0; i < kSI * kSR; ++i) {
-            const uint32_t p = i * kST + tid;
-            const uint64_t key = l0_key_of<BITS, CANON>(s_code, p, a.total_bits, a.symbols);
-            if (l0_valid(s_dol, p, a.symbols) && P0 + p < a.hi) atomicAdd(&s_hist[(uint32_t)(key >> osh)], 1u);
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < (1 << a.own_bits); i += kST)
-        if (s_hist[i]) atomicAdd(&ghist[i], s_hist[i]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// 2-bit packed copy of an ACGT sba: one u64 of codes (A0 C1 G2 T3, MSB first) and one u32 stop
-// mask ('$') per 32 positions -- the layout the L0 kernels build in LDS.  Packed once per sort and
-// read by every full-sequence pass (L0 count and partition; histogram, select count and store of
-// the key-range shards) instead of each pass re-packing the bytes: 0.28 B per position.
-// ---------------------------------------------------------------------------------------------
-template <bool NONACGT = false>
-__global__ __launch_bounds__(256) void pack2_kernel(const uint8_t *__restrict__ sba, uint64_t nwords,
-                                                    uint64_t *__restrict__ code, uint32_t *__restrict__ dol) {
-    for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < nwords; g += (uint64_t)gridDim.x * 256) {
-        uint64_t cw;
-        uint32_t dw;
-        pack2_word<NONACGT>(sba + 32 * g, cw, dw);
-        code[g] = cw;
-        dol[g] = dw;
-    }
-}
-
-// (the transfer's resident copy: stops at every non-ACGT byte, pack2_word<true>)
-hipError_t launch_pack2(const uint8_t *from, uint64_t nwords, uint64_t *code, uint32_t *dol, hipStream_t s) {
-    if (nwords == 0) return hipSuccess;
-    hipLaunchKernelGGL(pack2_kernel<true>, dim3((unsigned)std::min<uint64_t>((nwords + 255) / 256, 65536)), dim3(256),
-                       0, s, from, nwords, code, dol);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// column-wise segmented exclusive scan of per-tile digit histograms -> per-tile digit offsets
-// (one thread per digit: blockDim = RADIX)
-// ---------------------------------------------------------------------------------------------
-// Column scans of per-tile digit histograms.  Threads per block: min(RADIX, 1024); wider digit
-// spaces (the wide L0's 2048) take blockIdx.y for the digit block (chunk sums, tile apply) or
-// several consecutive digits per thread (the bucket scan).
-template <int RADIX>
-constexpr int scan_threads() { return RADIX < 1024 ? RADIX : 1024; }
-
-template <int RADIX>
-__global__ __launch_bounds__(scan_threads<RADIX>()) void chunk_sum_kernel(const uint32_t *__restrict__ tile_hist,
-                                                          const uint32_t *__restrict__ c_first,
-                                                          const uint32_t *__restrict__ c_ntiles,
-                                                          uint32_t *__restrict__ chunk_hist) {
-    const int d = blockIdx.y * scan_threads<RADIX>() + threadIdx.x;
-    const uint64_t f = c_first[blockIdx.x];
-    const uint32_t nt = c_ntiles[blockIdx.x];
-    uint32_t acc = 0;
-    uint32_t i = 0;
-    for (; i + 8 <= nt; i += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = tile_hist[(f + i + u) * RADIX + d];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += v[u];
-    }
-    for (; i < nt; ++i) acc += tile_hist[(f + i) * RADIX + d];
-    chunk_hist[(uint64_t)blockIdx.x * RADIX + d] = acc;
-}
-
-// one block per bucket: chunk bases within the bucket, digit bases, digit counts
-template <int RADIX>
-__global__ __launch_bounds__(scan_threads<RADIX>()) void seg_scan_kernel(uint32_t *__restrict__ chunk_hist,
-                                                         const uint32_t *__restrict__ s_cfirst,
-                                                         const uint32_t *__restrict__ s_nchunks,
-                                                         const uint32_t *__restrict__ s_start,
-                                                         uint32_t *__restrict__ seg_base, uint32_t *__restrict__ seg_cnt) {
-    constexpr int TH = scan_threads<RADIX>(), DPT = RADIX / TH;  // DPT consecutive digits per thread
-    __shared__ uint32_t s_wsum[TH / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t cf = s_cfirst[blockIdx.x];
-    const uint32_t nc = s_nchunks[blockIdx.x];
-    uint32_t run[DPT], sum = 0;
-#pragma unroll
-    for (int k = 0; k < DPT; ++k) {
-        const int d = t * DPT + k;
-        run[k] = 0;
-        for (uint32_t i = 0; i < nc; ++i) {
-            const uint32_t v = chunk_hist[(cf + i) * RADIX + d];
-            chunk_hist[(cf + i) * RADIX + d] = run[k];
-            run[k] += v;
-        }
-        sum += run[k];
-    }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (int w = 0; w < wave; ++w) pre += s_wsum[w];
-    uint32_t base = s_start[blockIdx.x] + pre + incl - sum;
-#pragma unroll
-    for (int k = 0; k < DPT; ++k) {
-        const int d = t * DPT + k;
-        seg_base[(uint64_t)blockIdx.x * RADIX + d] = base;
-        seg_cnt[(uint64_t)blockIdx.x * RADIX + d] = run[k];
-        for (uint32_t c = 0; c < nc; ++c) chunk_hist[(cf + c) * RADIX + d] += base;
-        base += run[k];
-    }
-}
-
-template <int RADIX>
-__global__ __launch_bounds__(scan_threads<RADIX>()) void tile_apply_kernel(uint32_t *__restrict__ tile_hist,
-                                                           const uint32_t *__restrict__ c_first,
-                                                           const uint32_t *__restrict__ c_ntiles,
-                                                           const uint32_t *__restrict__ chunk_base) {
-    const int d = blockIdx.y * scan_threads<RADIX>() + threadIdx.x;
-    const uint64_t f = c_first[blockIdx.x];
-    const uint32_t nt = c_ntiles[blockIdx.x];
-    uint32_t run = chunk_base[(uint64_t)blockIdx.x * RADIX + d];
-    uint32_t i = 0;
-    for (; i + 8 <= nt; i += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = tile_hist[(f + i + u) * RADIX + d];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            tile_hist[(f + i + u) * RADIX + d] = run;
-            run += v[u];
-        }
-    }
-    for (; i < nt; ++i) {
-        const uint32_t v = tile_hist[(f + i) * RADIX + d];
-        tile_hist[(f + i) * RADIX + d] = run;
-        run += v;
-    }
-}
-
-// wave-aggregated append of one entry per flagged lane; returns the entry index
-__device__ __forceinline__ uint32_t wave_append(bool flag, uint32_t *counter, int lane) {
-    const uint64_t m = __ballot(flag);
-    if (!m) return 0;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    return base + (uint32_t)__popcll(m & lt_mask);
-}
-
-// list counters (device, one array): next global level, done, then the local classes
-enum { kCtrBig = 0, kCtrDone = 1, kCtrLoc = 2, kLists = kCtrLoc + kLocal, kCtrNbCopy = kLists, kCtrN = 8 + 2 };
-// (kCtrNbCopy: the big list's count kept while its counter restarts, MsdDriver::drop_uniform_dev)
-// element sums per list, then the next global level's tile and chunk totals (its tile tables'
-// sizes, known with the list counts so that planning the level needs no read-back of its own)
-enum { kSumTiles = kLists, kSumChunks = kLists + 1, kSumN = kLists + 2 };
-
-__host__ __device__ inline uint32_t tiles_of(uint32_t len, uint32_t tile) { return (len + tile - 1) / tile; }
-__host__ __device__ inline uint32_t chunks_of(uint32_t len, uint32_t tile, uint32_t ctiles) {
-    return (tiles_of(len, tile) + ctiles - 1) / ctiles;
-}
-
-struct Lists {
-    uint32_t *nb_start, *nb_len;                 // buckets for the next global level
-    uint32_t *dn_start, *dn_len;                 // key bits exhausted: final as they stand
-    uint8_t *dn_par;
-    uint2 *loc[kLocal];                          // local entries by class
-    // per entry: the bucket's sorted key bits (its prefix), | kCompact when its elements are
-    // stored compact (a compact level's output, see level_pass); null: not recorded
-    uint64_t *nb_pref;
-    uint64_t *loc_pref[kLocal];
-};
-
-// A compact level writes per element, in the key array, the key bits below the next 8-bit digit
-// (high half) and the start (low half), and that digit in the digit bytes: 9 B instead of 12 (and
-// two stores instead of three); the bucket's prefix completes the key.
-constexpr uint64_t kCompact = 1ull << 63;
-
-__device__ __forceinline__ uint64_t compact_key(uint64_t pref, int hi, int B, uint32_t dig, uint32_t low) {
-    const int rem = B - hi;  // 9..40
-    return ((pref & ~kCompact) << rem) | ((uint64_t)dig << (rem - 8)) | (uint64_t)low;
-}
-
-// local class of a bucket of <= kBlockMax elements
-__host__ __device__ constexpr uint32_t local_cap(int cls) {
-    return cls == 0 ? 256 : cls == 1 ? 512 : cls == 2 ? 1024 : cls == 3 ? 4096 : cls == 5 ? 8192 : kTiny;
-}
-
-// list of a live sub-bucket of `size` elements (kCtr* index)
-__device__ __forceinline__ int list_of(uint32_t size, int hi, int B, bool allow_big) {
-    if (hi >= B) return kCtrDone;
-    if (size > (uint32_t)kBlockMax && allow_big) return kCtrBig;
-    if (size <= (uint32_t)kTiny) return kCtrLoc + 4;
-    return kCtrLoc + (size <= local_cap(0) ? 0 : size <= local_cap(1) ? 1 : size <= local_cap(2) ? 2
-                      : size <= local_cap(3) ? 3 : 5);
-}
-
-// entry `at` of list l for a sub-bucket
-__device__ __forceinline__ void put_entry(const Lists &L, int l, uint32_t at, uint32_t st, uint32_t size, int hi,
-                                          int parity, uint64_t pref = 0) {
-    // (global stores: flat ones, through pointers read from memory, would make every later
-    // memory wait of the kernel a full drain)
-    if (l == kCtrBig) {
-        gmem(L.nb_start)[at] = st;
-        gmem(L.nb_len)[at] = size;
-        if (L.nb_pref) gmem(L.nb_pref)[at] = pref;
-    } else if (l == kCtrDone) {
-        gmem(L.dn_start)[at] = st;
-        gmem(L.dn_len)[at] = size;
-        gmem(L.dn_par)[at] = (uint8_t)parity;
-    } else {
-        const uint2 le = local_entry(st, size, hi, parity);
-        gmem(reinterpret_cast<uint64_t *>(L.loc[l - kCtrLoc]))[at] = ((uint64_t)le.y << 32) | le.x;
-        if (L.loc_pref[l - kCtrLoc]) gmem(L.loc_pref[l - kCtrLoc])[at] = pref;
-    }
-}
-
-// route one sub-bucket (size >= 1) by size; hi = key bits sorted once it is cut out
-__device__ __forceinline__ void route(uint32_t st, uint32_t size, int hi, int B, int parity, bool allow_big,
-                                      const Lists &L, uint32_t *ctr, int lane) {
-    const int li = size >= 1 ? list_of(size, hi, B, allow_big) : -1;
-#pragma unroll
-    for (int l = 0; l < kLists; ++l) {
-        const uint32_t at = wave_append(li == l, &ctr[l], lane);
-        if (li == l) put_entry(L, l, at, st, size, hi, parity);
-    }
-}
-
-// The sub-buckets of one global level, one per thread: a workgroup-aggregated append (one
-// atomic per list per workgroup) into the next-level / done / block-local / wave-local lists;
-// sums[l] += elements routed to list l (for the profile's work counts).
-constexpr int kClassT = 1024;
-
-// Prefixes: sub-bucket i of a partition by pw-bit digits has parent i >> pw (prefix ppref[i >> pw],
-// 0 when null) and digit i & (2^pw - 1); with pw = 0 the entries are whole buckets (prefix ppref[i]).
-// compact: the level wrote compact elements (the entries get kCompact).
-__global__ __launch_bounds__(kClassT) void classify_kernel(const uint32_t *__restrict__ seg_base,
-                                                           const uint32_t *__restrict__ seg_cnt, uint64_t nsub, int hi,
-                                                           int B, int parity, Lists L, uint32_t *__restrict__ ctr,
-                                                           unsigned long long *__restrict__ sums, uint32_t min_size,
-                                                           const uint64_t *__restrict__ ppref, int pw, int compact,
-                                                           uint32_t tile, uint32_t ctiles) {
-    constexpr int NW = kClassT / 64;
-    __shared__ uint32_t s_cnt[kLists][NW];
-    __shared__ uint32_t s_elems[kLists][NW];
-    __shared__ uint32_t s_base[kLists];
-    __shared__ uint32_t s_tc[2][NW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t i = (uint64_t)blockIdx.x * kClassT + tid;
-    const uint32_t size = i < nsub ? seg_cnt[i] : 0, st = i < nsub ? seg_base[i] : 0;
-    const int li = size >= min_size ? list_of(size, hi, B, true) : -1;
-    bool f[kLists];
-#pragma unroll
-    for (int l = 0; l < kLists; ++l) f[l] = li == l;
-    uint32_t below[kLists];
-#pragma unroll
-    for (int l = 0; l < kLists; ++l) {
-        const uint64_t m = __ballot(f[l]);
-        below[l] = lanes_below(m);
-        uint32_t e = f[l] ? size : 0;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
-        if (lane == 0) {
-            s_cnt[l][wave] = (uint32_t)__popcll(m);
-            s_elems[l][wave] = e;
-        }
-    }
-    {
-        uint32_t tl = li == kCtrBig ? tiles_of(size, tile) : 0, ch = li == kCtrBig ? chunks_of(size, tile, ctiles) : 0;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            tl += __shfl_xor(tl, off);
-            ch += __shfl_xor(ch, off);
-        }
-        if (lane == 0) {
-            s_tc[0][wave] = tl;
-            s_tc[1][wave] = ch;
-        }
-    }
-    __syncthreads();
-    if (tid >= 64 && tid < 66) {  // (another wave than the list totals below)
-        unsigned long long t = 0;
-        for (int w = 0; w < NW; ++w) t += s_tc[tid - 64][w];
-        if (t) atomicAdd(&sums[kSumTiles + tid - 64], t);
-    }
-    if (tid < kLists) {
-        uint32_t tot = 0;
-        unsigned long long el = 0;
-        for (int w = 0; w < NW; ++w) {
-            tot += s_cnt[tid][w];
-            el += s_elems[tid][w];
-        }
-        s_base[tid] = tot ? atomicAdd(&ctr[tid], tot) : 0;
-        if (el) atomicAdd(&sums[tid], el);
-    }
-    __syncthreads();
-    uint32_t at[kLists];
-#pragma unroll
-    for (int l = 0; l < kLists; ++l) {
-        uint32_t pre = s_base[l];
-        for (int w = 0; w < wave; ++w) pre += s_cnt[l][w];
-        at[l] = pre + below[l];
-    }
-    uint64_t pref = 0;
-    if (li >= 0) {
-        if (pw > 0) pref = ((ppref ? ppref[i >> pw] & ~kCompact : 0ull) << pw) | (i & ((1ull << pw) - 1));
-        else pref = ppref ? ppref[i] & ~kCompact : 0ull;
-        if (compact) pref |= kCompact;
-    }
-#pragma unroll
-    for (int l = 0; l < kLists; ++l)
-        if (li == l) put_entry(L, l, at[l], st, size, hi, parity, pref);
-}
-
-// workgroups per bucket (grid.y) of the per-bucket copy kernels below: the buckets they see are
-// few but can be huge (a repeat's group of identical k-mers: 250 K elements at C4), and one
-// workgroup walking such a bucket alone took 3 ms per C4 rank
-static unsigned bucket_split(uint64_t nbuckets) { return nbuckets <= 4096 ? 32u : nbuckets <= 65536 ? 4u : 1u; }
-
-// (key, start) of packed-pair elements (a MODE 5 level's output, gkm_partition.h) in place, for
-// the buckets a packed-pair level's output goes to that do not read pairs: the next level when it
-// is not compact, and the local finishing classes.  Bucket j: start bst[j], length blen[j], sorted
-// key bits bpref[j] (the top hi of B); gridDim.y workgroups per bucket.
-__global__ __launch_bounds__(256) void expand_pair_kernel(const uint32_t *__restrict__ bst,
-                                                          const uint32_t *__restrict__ blen,
-                                                          const uint64_t *__restrict__ bpref, int hi, int B, int shi,
-                                                          uint64_t *__restrict__ kio, const uint16_t *__restrict__ in16,
-                                                          uint32_t *__restrict__ vout) {
-    const uint64_t st = bst[blockIdx.x];
-    const uint32_t len = blen[blockIdx.x];
-    const uint64_t top = (bpref[blockIdx.x] & ~kCompact) << (B - hi);
-    for (uint32_t e = blockIdx.y * 256 + threadIdx.x; e < len; e += gridDim.y * 256) {
-        uint64_t key;
-        uint32_t val;
-        unpack_pair(kio[st + e], in16[st + e], shi, key, val);
-        kio[st + e] = top | key;
-        vout[st + e] = val;
-    }
-}
-
-// the same over local-list entries [first, first + count) (entry: start, len << 8 | hi << 1 | parity;
-// prefixes in pref[]) -- the local buckets a packed-pair level's classify listed
-__global__ __launch_bounds__(256) void expand_pair_list_kernel(const uint2 *__restrict__ list,
-                                                               const uint64_t *__restrict__ pref, uint32_t first,
-                                                               int B, int shi, uint64_t *__restrict__ kio,
-                                                               const uint16_t *__restrict__ in16,
-                                                               uint32_t *__restrict__ vout) {
-    const uint2 en = list[first + blockIdx.x];
-    const uint64_t st = en.x;
-    const uint32_t len = en.y >> 8;
-    const int hi = (en.y >> 1) & 127;
-    const uint64_t top = (pref[first + blockIdx.x] & ~kCompact) << (B - hi);
-    for (uint32_t e = threadIdx.x; e < len; e += 256) {
-        uint64_t key;
-        uint32_t val;
-        unpack_pair(kio[st + e], in16[st + e], shi, key, val);
-        kio[st + e] = top | key;
-        vout[st + e] = val;
-    }
-}
-
-// packed-L0 elements (P88: the digit byte above a packed pair) -> (key bits below the sorted ones,
-// start)
-__device__ __forceinline__ void unpack_p88(uint64_t a, uint32_t lo, uint32_t dg, int shi, uint64_t &rel, uint32_t &val) {
-    unpack_pair(a, lo, shi, rel, val);
-    rel |= (uint64_t)dg << (64 - shi);
-}
-
-// (key, start) of packed-L0 elements in place, for the buckets whose next reader does not take the
-// packed form: the big buckets when the level behind the L0 writes no packed pairs itself (gridDim.y
-// workgroups per bucket), and the local classes' entries (expand_p88_list_kernel)
-__global__ __launch_bounds__(256) void expand_p88_kernel(const uint32_t *__restrict__ bst,
-                                                         const uint32_t *__restrict__ blen,
-                                                         const uint64_t *__restrict__ bpref, int hi, int B, int shi,
-                                                         uint64_t *__restrict__ kio, const uint16_t *__restrict__ in16,
-                                                         const uint8_t *__restrict__ in8, uint32_t *__restrict__ vout) {
-    const uint64_t st = bst[blockIdx.x];
-    const uint32_t len = blen[blockIdx.x];
-    const uint64_t top = (bpref[blockIdx.x] & ~kCompact) << (B - hi);
-    for (uint32_t e = blockIdx.y * 256 + threadIdx.x; e < len; e += gridDim.y * 256) {
-        uint64_t rel;
-        uint32_t val;
-        unpack_p88(kio[st + e], in16[st + e], in8[st + e], shi, rel, val);
-        kio[st + e] = top | rel;
-        vout[st + e] = val;
-    }
-}
-
-__global__ __launch_bounds__(256) void expand_p88_list_kernel(const uint2 *__restrict__ list,
-                                                              const uint64_t *__restrict__ pref, int B, int shi,
-                                                              uint64_t *__restrict__ kio, const uint16_t *__restrict__ in16,
-                                                              const uint8_t *__restrict__ in8,
-                                                              uint32_t *__restrict__ vout) {
-    const uint2 en = list[blockIdx.x];
-    const uint64_t st = en.x;
-    const uint32_t len = en.y >> 8;
-    const int hi = (en.y >> 1) & 127;
-    const uint64_t top = (pref[blockIdx.x] & ~kCompact) << (B - hi);
-    for (uint32_t e = threadIdx.x; e < len; e += 256) {
-        uint64_t rel;
-        uint32_t val;
-        unpack_p88(kio[st + e], in16[st + e], in8[st + e], shi, rel, val);
-        kio[st + e] = top | rel;
-        vout[st + e] = val;
-    }
-}
-
-// the same over pieces (first_level_from_pieces: the prefetched L0's region buckets): piece j at
-// pp[j], pp[np + j] elements, its bucket (the top hi key bits) pp[2 np + j]
-__global__ __launch_bounds__(256) void expand_p88_pieces_kernel(const uint64_t *__restrict__ pp, uint32_t np, int hi,
-                                                                int B, int shi, uint64_t *__restrict__ kio,
-                                                                const uint16_t *__restrict__ in16,
-                                                                const uint8_t *__restrict__ in8,
-                                                                uint32_t *__restrict__ vout) {
-    const uint64_t st = pp[blockIdx.x], len = pp[np + blockIdx.x];
-    const uint64_t top = pp[2 * (uint64_t)np + blockIdx.x] << (B - hi);
-    for (uint64_t e = blockIdx.y * 256 + threadIdx.x; e < len; e += gridDim.y * 256) {
-        uint64_t rel;
-        uint32_t val;
-        unpack_p88(kio[st + e], in16[st + e], in8[st + e], shi, rel, val);
-        kio[st + e] = top | rel;
-        vout[st + e] = val;
-    }
-}
-
-// keys of compact elements (gridDim.y workgroups per bucket): prefix | digit | low bits
-__global__ __launch_bounds__(256) void expand_compact_kernel(const uint32_t *__restrict__ bst,
-                                                             const uint32_t *__restrict__ blen,
-                                                             const uint64_t *__restrict__ bpref, int hi, int B,
-                                                             const uint8_t *__restrict__ nd,
-                                                             uint64_t *__restrict__ kio, uint32_t *__restrict__ vout,
-                                                             const uint32_t *__restrict__ nb_dev = nullptr) {
-    if (nb_dev && blockIdx.x >= *nb_dev) return;  // (a grid sized by a bound: the count is on the device)
-    const uint64_t st = bst[blockIdx.x];
-    const uint32_t len = blen[blockIdx.x];
-    const uint64_t pf = bpref[blockIdx.x];
-    for (uint32_t e = blockIdx.y * 256 + threadIdx.x; e < len; e += gridDim.y * 256) {
-        const uint64_t x = kio[st + e];
-        kio[st + e] = compact_key(pf, hi, B, nd[st + e], (uint32_t)(x >> 32));
-        vout[st + e] = (uint32_t)x;
-    }
-}
-
-// tile + chunk tables of a bucket list (one thread per bucket)
-// per-tile (start, count) and per-chunk (first tile, tiles) tables of the nseg buckets of a level:
-// one thread per tile (j < T) and per chunk (j < C), each finding its bucket by a binary search over
-// the buckets' first tile / first chunk (one thread per bucket wrote a whole bucket's tiles
-// serially: 0.6 ms for the one 387 M-key bucket of a key-range rank at N = 8)
-__device__ __forceinline__ uint32_t owner_of(const uint32_t *__restrict__ first, uint32_t n, uint32_t j) {
-    uint32_t lo = 0, hi = n;  // the last bucket with first <= j
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (first[mid] <= j) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void tile_table_kernel(const uint32_t *__restrict__ s_start,
-                                                         const uint32_t *__restrict__ s_len,
-                                                         const uint32_t *__restrict__ s_tfirst,
-                                                         const uint32_t *__restrict__ s_cfirst, uint32_t nseg,
-                                                         uint32_t tile, uint32_t T, uint32_t C, uint32_t ctiles,
-                                                         uint32_t *__restrict__ t_start,
-                                                         uint32_t *__restrict__ t_count, uint32_t *__restrict__ c_first,
-                                                         uint32_t *__restrict__ c_ntiles) {
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j < T) {
-        const uint32_t s = owner_of(s_tfirst, nseg, j);
-        const uint32_t r = j - s_tfirst[s], len = s_len[s];
-        t_start[j] = s_start[s] + r * tile;
-        t_count[j] = std::min<uint32_t>(tile, len - r * tile);
-    }
-    if (j < C) {
-        const uint32_t s = owner_of(s_cfirst, nseg, j);
-        const uint32_t r = j - s_cfirst[s], nt = (s_len[s] + tile - 1) / tile;
-        c_first[j] = s_tfirst[s] + r * ctiles;
-        c_ntiles[j] = std::min<uint32_t>(ctiles, nt - r * ctiles);
-    }
-}
-
-__global__ __launch_bounds__(256) void seg_counts_kernel(const uint32_t *__restrict__ s_len, uint32_t nseg,
-                                                         uint32_t tile, uint32_t ctiles, uint32_t *__restrict__ ntiles,
-                                                         uint32_t *__restrict__ nchunks) {
-    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= nseg) return;
-    const uint32_t nt = (s_len[s] + tile - 1) / tile;
-    ntiles[s] = nt;
-    nchunks[s] = (nt + ctiles - 1) / ctiles;
-}
-
-// seg_counts_kernel and the exclusive scans of both counts in ONE workgroup, for the level's
-// bucket list of up to kSegScanMax entries (C3: 128 / 32 K buckets; the deep levels of a repeat-rich
-// genome: tens): one launch instead of seven, the totals already known from the list counters
-constexpr uint32_t kSegScanMax = 1u << 16;
-__global__ __launch_bounds__(1024) void seg_tiles_scan_kernel(const uint32_t *__restrict__ s_len, uint32_t nseg,
-                                                              uint32_t tile, uint32_t ctiles,
-                                                              uint32_t *__restrict__ tfirst,
-                                                              uint32_t *__restrict__ cfirst,
-                                                              uint32_t *__restrict__ nchunks) {
-    __shared__ uint32_t s_w[2][16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t carry_t = 0, carry_c = 0;
-    for (uint32_t b0 = 0; b0 < nseg; b0 += 1024) {  // (block-uniform)
-        const uint32_t s = b0 + tid;
-        const uint32_t nt = s < nseg ? tiles_of(s_len[s], tile) : 0, nc = (nt + ctiles - 1) / ctiles;
-        const uint32_t it = wave_incl_scan(nt), ic = wave_incl_scan(nc);
-        if (lane == 63) {
-            s_w[0][wave] = it;
-            s_w[1][wave] = ic;
-        }
-        __syncthreads();
-        uint32_t pt = carry_t, pc = carry_c;
-        for (int w = 0; w < 16; ++w) {
-            const uint32_t a = s_w[0][w], d = s_w[1][w];
-            if (w < wave) {
-                pt += a;
-                pc += d;
-            }
-            carry_t += a;
-            carry_c += d;
-        }
-        if (s < nseg) {
-            tfirst[s] = pt + it - nt;
-            cfirst[s] = pc + ic - nc;
-            nchunks[s] = nc;
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// local rounds: a bucket of <= T*I elements per workgroup, persistent over a list
-// ---------------------------------------------------------------------------------------------
-// Per bucket (entry = start, len, hi, parity):
-//   1. stable partition by the R-bit digit below the top `hi` bits into LDS (partition_stage);
-//   2. each sub-bucket: singleton, or no key bits left after this digit (equal keys, already in
-//      start order) -> final; <= kSmall -> rank-by-count on the key (ties: staging order =
-//      start order); larger -> left in stable order and re-listed for the next round (its head
-//      flags are provisional: that round rewrites them);
-//   3. keys, starts and head flags (key differs from its predecessor) are written back in order.
-// Output always goes to buffer 0; the bucket is read fully before any write, so in place is safe.
-// Loads and stores are branch-free with static counts (clamped to the bucket), so the next
-// bucket's loads -- issued once the current one is final in LDS -- overlap its stores.
-// Common-prefix skip: x_or = OR over a bucket's keys of (key ^ first key).  The bits of the key
-// below the hi sorted ones that are equal in every element need no partition pass: the bucket's
-// next digit starts at its highest differing bit.  All keys equal: one last digit (one sub-bucket,
-// final).  Repeats make such buckets common (a 30-copy repeat k-mer would otherwise take one round
-// per 8 bits).
-__device__ __forceinline__ int skip_hi(uint64_t x_or, int B, int hi) {
-    const int rem = B - hi;
-    if (rem <= 0) return hi;
-    x_or &= rem >= 64 ? ~0ull : ((1ull << rem) - 1);
-    if (x_or == 0) return max(hi, B - 8);
-    return B - 1 - (63 - __clzll(x_or));
-}
-
-__device__ __forceinline__ uint64_t wave_or64(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x |= __shfl_xor(x, off);
-    return x;
-}
-
-// compact inputs (first local round after a compact level): where to find the elements' low key
-// bits and next digits, and the entries' prefixes
-struct CompactIn {
-    const uint64_t *pref;  // per list entry (null: no entry is compact)
-    const uint8_t *nd;
-};
-
-template <int T, int I>
-__device__ __forceinline__ void local_load(const uint2 e, const uint64_t *k0, const uint32_t *v0, const uint64_t *k1,
-                                           const uint32_t *v1, uint64_t (&key)[I], uint32_t (&val)[I],
-                                           uint64_t pf = 0, const CompactIn *ci = nullptr, int B = 0) {
-    const uint64_t st = e.x;
-    const uint32_t len = e.y >> 8;
-    const uint64_t *sk = (e.y & 1) ? k1 : k0;
-    const uint32_t *sv = (e.y & 1) ? v1 : v0;
-    uint32_t q0 = (threadIdx.x >> 6) * (I * 64) + (threadIdx.x & 63);
-    asm volatile("" : "+v"(q0));
-    if (pf & kCompact) {  // (uniform: one bucket per wave / workgroup)
-        const int hi = (e.y >> 1) & 127;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint64_t e_ = st + min(q0 + i * 64, len - 1);
-            const uint64_t x = sk[e_];
-            key[i] = compact_key(pf, hi, B, ci->nd[e_], (uint32_t)(x >> 32));
-            val[i] = (uint32_t)x;
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < I; ++i) {
-        const uint64_t e_ = st + min(q0 + i * 64, len - 1);
-        key[i] = sk[e_];
-        val[i] = sv[e_];
-    }
-}
-
-template <int T, int I, int R>
-__global__ __launch_bounds__(T) void msd_local_kernel(const uint2 *__restrict__ list, uint32_t count, int B,
-                                                      uint64_t *k0, uint32_t *v0, const uint64_t *k1,
-                                                      const uint32_t *v1, uint8_t *__restrict__ heads, Lists L,
-                                                      uint32_t *__restrict__ ctr, int skip, uint32_t small, int wkeys,
-                                                      CompactIn ci) {
-    using SM = PartSmem<T, I, R>;
-    constexpr int TILE = SM::kTile;
-    constexpr int RADIX = SM::kRadix;
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[SM::kUnion];
-    __shared__ uint32_t s_wsum[SM::kWaves];
-    __shared__ uint32_t s_start[RADIX + 1];
-    __shared__ uint8_t s_hd[TILE + 1];
-    __shared__ uint32_t s_any;
-    __shared__ uint64_t s_kf, s_or;                  // common-prefix skip: first key, OR of differences
-    uint64_t *s_k = reinterpret_cast<uint64_t *>(s_raw);
-    uint32_t *s_v = reinterpret_cast<uint32_t *>(s_raw + SM::kValOff);
-    uint32_t *s_wc = reinterpret_cast<uint32_t *>(s_raw);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t idx = blockIdx.x;
-    if (idx >= count) return;
-    uint2 e = list[idx];
-    uint64_t pf = ci.pref ? ci.pref[idx] : 0;
-    uint64_t key[I];
-    uint32_t val[I];
-    local_load<T, I>(e, k0, v0, k1, v1, key, val, pf, &ci, B);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (; idx < count; idx += gridDim.x) {
-        const uint2 ce = e;
-        const uint64_t st = ce.x;
-        const uint32_t len = ce.y >> 8;
-        int hi = (ce.y >> 1) & 127;
-        if (skip) {
-            if (tid == 0) {
-                s_kf = key[0];
-                s_or = 0;
-            }
-            lds_barrier();
-            uint64_t x = 0;
-#pragma unroll
-            for (int i = 0; i < I; ++i)
-                if ((uint32_t)(wave * (I * 64) + i * 64 + lane) < len) x |= key[i] ^ s_kf;
-            x = wave_or64(x);
-            if (lane == 0 && x) atomicOr((unsigned long long *)&s_or, (unsigned long long)x);
-            lds_barrier();
-            hi = skip_hi(s_or, B, hi);
-        }
-        const Dig dd = dig_at(B, hi, R);
-        const int nhi = hi + R;      // key bits sorted within a sub-bucket
-        const bool last = nhi >= B;  // sub-bucket keys are equal
-        if (idx + gridDim.x < count) {  // else: re-load the current one
-            e = list[idx + gridDim.x];
-            pf = ci.pref ? ci.pref[idx + gridDim.x] : 0;
-        }
-
-        // 1. stable partition into LDS
-        for (int i = tid; i < SM::kWaves * RADIX; i += T) s_wc[i] = 0;
-        if (tid == 0) s_any = 0;
-        lds_barrier();
-        bool valid[I];
-        uint32_t slot[I];
-#pragma unroll
-        for (int i = 0; i < I; ++i) valid[i] = (uint32_t)(wave * (I * 64) + i * 64 + lane) < len;
-        // items of this wave holding elements (wave-uniform)
-        const int wbase = wave * (I * 64);
-        const int live = (int)len > wbase ? min(I, ((int)len - wbase + 63) >> 6) : 0;
-        partition_stage<T, I, R>(key, val, valid, dd, s_raw, nullptr, s_wsum, s_start, slot, nullptr, live);
-
-        // 2. final position and head flag of every element
-        uint32_t out[I];
-        uint8_t hd[I];
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            out[i] = slot[i];
-            hd[i] = 0;
-            if (i >= live) continue;  // wave-uniform
-            const uint32_t dg = dg_of(key[i], dd);
-            const uint32_t sb = s_start[dg], size = s_start[dg + 1] - sb;
-            hd[i] = slot[i] == sb;  // singleton or equal keys: the first is the head
-            if (valid[i] && size > 1 && !last) {
-                if (size <= small) {
-                    const uint32_t me = slot[i] - sb;
-                    uint32_t lt = 0, eq = 0;
-                    for (uint32_t j = 0; j < size; ++j) {
-                        const uint64_t kj = s_k[sb + j];
-                        lt += kj < key[i];
-                        eq += kj == key[i] && j < me;
-                    }
-                    out[i] = sb + lt + eq;
-                    hd[i] = eq == 0;
-                } else {
-                    hd[i] = 2;  // not final: re-listed, head written by the next round
-                }
-            }
-        }
-        // re-list the large sub-buckets (rare): one entry each, from its first element
-        bool first[I], any = false;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            first[i] = valid[i] && hd[i] == 2 && slot[i] == s_start[dg_of(key[i], dd)];
-            any |= first[i];
-        }
-        if (any) s_any = 1;
-        lds_barrier();  // also: every rank-by-count read is done before the staging is overwritten
-        const bool relist = s_any != 0;
-        if (relist) {
-#pragma unroll
-            for (int i = 0; i < I; ++i) {
-                const uint32_t dg = dg_of(key[i], dd);
-                const uint32_t size = first[i] ? s_start[dg + 1] - s_start[dg] : 0;
-                route((uint32_t)st + slot[i], size, nhi, B, 0, false, L, ctr, lane);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < I; ++i) {  // invalid items: out = sink slot
-            if (i >= live) continue;
-            s_k[out[i]] = key[i];
-            s_v[out[i]] = val[i];
-            s_hd[out[i]] = hd[i];  // 0 / 1: final (not) a group head; 2: re-listed
-        }
-        // the next bucket's loads fly while this one is written back
-        local_load<T, I>(e, k0, v0, k1, v1, key, val, pf, &ci, B);  // unconditional: static load count
-        lds_barrier();
-
-        // 3. in-order write-back with head flags
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint32_t p = min((uint32_t)(i * T + tid), len - 1);
-            if (relist || wkeys) k0[st + p] = s_k[p];  // keys: final-key sorts, or re-listed elements
-            v0[st + p] = s_v[p];
-            heads[st + p] = s_hd[p] & 1;
-        }
-        lds_barrier();  // the write-back has read LDS before the next bucket's staging
-    }
-}
-
-// list entry j of a wave class (scalar loads) and its prefix (0: not recorded)
-__device__ __forceinline__ void wave_entry(const uint2 *__restrict__ list, const uint64_t *__restrict__ cpref,
-                                           uint32_t j, uint2 &e, uint64_t &pf) {
-    e = list[j];
-    pf = cpref ? cpref[j] : 0ull;
-}
-
-// raw elements of a wave-class bucket: compact (x = low << 32 | start, next-digit byte) or full
-// (key, start).  One global load instruction per word either way (so the compiler's count of
-// loads in flight is static); buffers chosen by integer selects (pointer selects between kernel
-// arguments went through the stack as flat loads).  Loads clamped to the bucket.
-template <int I>
-__device__ __forceinline__ void wave_load(const uint2 e, uint64_t pf, int lane, const uint64_t *k0, const uint64_t *k1,
-                                          const uint32_t *v0, const uint32_t *v1, const uint8_t *cnd,
-                                          uint64_t (&a)[I], uint32_t (&b)[I]) {
-    const uint64_t st = e.x;
-    const uint32_t len = e.y >> 8;
-    const bool p1 = (e.y & 1) != 0, cmp = (pf & kCompact) != 0;
-    const uint64_t kb = p1 ? (uint64_t)k1 : (uint64_t)k0;
-    const uint64_t bb = cmp ? (uint64_t)cnd : (p1 ? (uint64_t)v1 : (uint64_t)v0);
-    const int sh = cmp ? 0 : 2;
-    uint32_t q = lane;
-    asm volatile("" : "+v"(q));
-    if (cmp) {  // byte loads of the digits: 0.1-0.3 ms faster than unaligned 4-byte ones at C3 (A/B)
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            const uint64_t at = st + min(q + i * 64, len - 1);
-            a[i] = *reinterpret_cast<gu64 *>(kb + 8 * at);
-            b[i] = *reinterpret_cast<gu8 *>(bb + at);
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < I; ++i) {
-        const uint64_t at = st + min(q + i * 64, len - 1);
-        a[i] = *reinterpret_cast<gu64 *>(kb + 8 * at);
-        b[i] = *reinterpret_cast<gu32u *>(bb + (at << sh));
-    }
-}
-
-// Single-wave finishing kernel for buckets of <= 64 I elements (C3: ~370 keys behind the compact
-// level, class 1).  Per bucket, one wave:
-//   keys   compact entries (a compact level's output): key = prefix | next-digit byte | low bits
-//          (compact_key); full entries: (key, start) as stored
-//   rank   the next 8-bit digit of every element, ranked by ONE returning LDS atomic per item
-//          (rank_atomic: stable); the 256 digit counts are scanned 4 per lane (wave_incl_scan)
-//   order  each digit's elements take its slots in stable order; the key bits below the digit are
-//          staged at those slots, and a sub-bucket of 2..small elements is ordered by
-//          rank-by-count over them (ties: staging order = start order); larger sub-buckets are
-//          re-listed for another round; a sub-bucket whose key bits are exhausted is final
-//   write  keys (the group-head flag in bit 63 when B < 64) and starts staged at their final slots,
-//          then stored contiguously: keys, starts and head flags of the whole bucket
-// The next bucket's elements are loaded once the current one is staged in LDS, so they fly during
-// its write-back; loads and write-back are branch-free with static counts (slots clamped to the
-// bucket), so the next iteration waits for those loads without draining the stores.  The list entries and prefixes are scalar loads two
-// buckets ahead.  LDS per wave: staged keys (aliased by the low bits of the ranking: one wave's LDS
-// operations complete in order), staged starts, digit counts -- 7.2 KB at I = 8.
-// WK: keys are written back (one-word sorts); otherwise only for buckets with re-listed elements.
-template <int I, int MINW, bool WK, int R>
-__global__ __launch_bounds__(64, MINW) void msd_wave_kernel(const uint2 *__restrict__ list, uint32_t count, int B,
-                                                      uint64_t *k0, uint32_t *v0, const uint64_t *k1,
-                                                      const uint32_t *v1, uint8_t *__restrict__ heads,
-                                                      const Lists *__restrict__ Lp, uint32_t *__restrict__ ctr,
-                                                      int skip, uint32_t small, const uint64_t *__restrict__ cpref,
-                                                      const uint8_t *__restrict__ cnd) {
-    constexpr int CAP = 64 * I;
-    // bit budget of the packed per-item words below: sub-bucket start (slot) in 10 bits, size in 11,
-    // rank in 11, and the slot in the low 10 bits of a composite rank-by-count value
-    static_assert(CAP <= 1024, "slot fields are 10 bits wide");
-    constexpr int MINLIVE = I > 4 ? I / 2 + 1 : 1;  // items a bucket of the class always fills
-    constexpr int RADIX = 1 << R, CPL = RADIX / 64;  // digits; counters per lane in the scan
-    static_assert(CPL % 4 == 0, "16-byte counter groups");
-    __shared__ uint64_t s_k[CAP + 4];  // staged keys (slot CAP: sink); rank-by-count values + sentinels
-    // digit counts -> starts (s_cnt[RADIX] = len); once the ranks are final, the staged starts
-    // (slot CAP: sink) -- one wave's LDS operations complete in order
-    constexpr int kUnion = (RADIX + 4) > (CAP + 1) ? (RADIX + 4) : (CAP + 1);
-    __shared__ __attribute__((aligned(16))) uint32_t s_cv[kUnion];
-    uint32_t *const s_cnt = s_cv;
-    uint32_t *const s_v = s_cv;
-    const int lane = threadIdx.x;
-    // XCD-aware walk (grid a multiple of 8): workgroup b takes the (b % 8)-th eighth of the list,
-    // so the list's neighbouring buckets -- neighbours in memory, since classify appends a level's
-    // sub-buckets in runs of address order -- are finished at about the same time on one XCD and
-    // share the L2 lines at their edges; other grids walk the list with the plain stride
-    uint32_t idx = blockIdx.x, lend = count, lstep = gridDim.x;
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-        const uint32_t x = blockIdx.x & 7;
-        idx = (uint32_t)((uint64_t)count * x / 8) + (blockIdx.x >> 3);
-        lend = (uint32_t)((uint64_t)count * (x + 1) / 8);
-        lstep = gridDim.x >> 3;
-    }
-    if (idx >= lend) return;
-    // keys and starts of a bucket from its raw elements
-    auto unpack = [B](const uint2 e, uint64_t pf, const uint64_t (&a)[I], const uint32_t (&b)[I], uint64_t (&key)[I],
-                      uint32_t (&val)[I]) {
-        const int hi0 = (e.y >> 1) & 127;
-        const bool cmp = (pf & kCompact) != 0;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            key[i] = cmp ? compact_key(pf, hi0, B, b[i] & 0xFFu, (uint32_t)(a[i] >> 32)) : a[i];
-            val[i] = cmp ? (uint32_t)a[i] : b[i];
-        }
-    };
-    uint2 e, en;
-    uint64_t pf, pfn;
-    uint64_t key[I], a[I];
-    uint32_t val[I], b[I];
-    wave_entry(list, cpref, idx, e, pf);
-    wave_load<I>(e, pf, lane, k0, k1, v0, v1, cnd, a, b);
-    en = e;
-    pfn = pf;
-    if (idx + lstep < lend) wave_entry(list, cpref, idx + lstep, en, pfn);
-    __builtin_amdgcn_s_waitcnt(kVmcnt0);
-    for (;;) {
-        const uint64_t st = e.x;
-        const uint32_t len = e.y >> 8;
-        const int hi0 = (e.y >> 1) & 127;
-        unpack(e, pf, a, b, key, val);
-        uint2 enn = en;
-        uint64_t pfnn = pfn;
-        if (idx + 2 * lstep < lend) wave_entry(list, cpref, idx + 2 * lstep, enn, pfnn);
-
-        int hi = hi0;
-        if (skip) {  // common-prefix skip (later rounds and phases: repeats)
-            const uint64_t kf = ((uint64_t)__builtin_amdgcn_readlane((int)(uint32_t)(key[0] >> 32), 0) << 32) |
-                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key[0], 0);
-            uint64_t x = 0;
-#pragma unroll
-            for (int i = 0; i < I; ++i)
-                if ((uint32_t)(i * 64 + lane) < len) x |= key[i] ^ kf;
-            hi = skip_hi(wave_or64(x), B, hi);
-        }
-        const Dig dd = dig_at(B, hi, R);
-        const bool last = hi + R >= B;                      // a sub-bucket's keys are equal
-        const uint64_t lowm = (1ull << dd.shift) - 1ull;    // key bits below the digit
-        const int live = min(I, (int)((len + 63) >> 6));    // items holding elements (wave-uniform)
-
-        // 1. stable rank inside the digit
-#pragma unroll
-        for (int u = 0; u < CPL / 4; ++u) reinterpret_cast<uint4 *>(s_cnt)[lane * (CPL / 4) + u] = make_uint4(0, 0, 0, 0);
-        uint32_t pk[I];  // rank | digit << 16, then rank << 21 | size << 10 | sub-bucket start
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            pk[i] = 0;
-            if (i >= live) continue;
-            const uint32_t d = dg_of(key[i], dd);
-            pk[i] = rank_atomic(s_cnt, d, (uint32_t)(i * 64 + lane) < len) | (d << 16);
-        }
-        // 2. digit starts (exclusive scan of the RADIX counts, CPL per lane); s_cnt[RADIX] = len
-        {
-            uint4 c[CPL / 4];
-            uint32_t sl = 0;
-#pragma unroll
-            for (int u = 0; u < CPL / 4; ++u) {
-                c[u] = reinterpret_cast<const uint4 *>(s_cnt)[lane * (CPL / 4) + u];
-                sl += c[u].x + c[u].y + c[u].z + c[u].w;
-            }
-            const uint32_t incl = wave_incl_scan(sl);
-            uint32_t r0 = incl - sl;
-#pragma unroll
-            for (int u = 0; u < CPL / 4; ++u) {
-                const uint4 o = make_uint4(r0, r0 + c[u].x, r0 + c[u].x + c[u].y, r0 + c[u].x + c[u].y + c[u].z);
-                reinterpret_cast<uint4 *>(s_cnt)[lane * (CPL / 4) + u] = o;
-                r0 = o.w + c[u].w;
-            }
-            if (lane == 63) s_cnt[RADIX] = incl;
-        }
-        // 3. slots.  Staged at each element's slot: its key bits below the sorted ones (digit and
-        // low bits) with the slot appended -- (x << 10) | slot, unique, and in sub-bucket order
-        // exactly the stable order -- when they fit 64 bits; otherwise the low bits alone.  Four
-        // sentinels (all ones) follow the bucket, so a rank-by-count may read past its sub-bucket
-        // unpredicated: later digits and sentinels are larger than any of its values.
-        const bool cmpst = hi + 64 - 10 >= B;  // composite values (C3: 39 + 10 bits)
-        const uint64_t xm = B - hi >= 64 ? ~0ull : (1ull << (B - hi)) - 1ull;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            if (i >= live) continue;
-            const uint32_t d = pk[i] >> 16, r = pk[i] & 0xFFFFu;
-            const uint32_t sb = s_cnt[d], size = s_cnt[d + 1] - sb;
-            if ((uint32_t)(i * 64 + lane) < len)
-                s_k[sb + r] = cmpst ? ((key[i] & xm) << 10) | (sb + r) : key[i] & lowm;
-            pk[i] = (r << 21) | (size << 10) | sb;
-        }
-        if (lane < 4) s_k[len + lane] = ~0ull;
-        // 4. final slot of every element: sub-buckets of 2..small elements by rank-by-count
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            if (i >= live) continue;
-            const uint32_t sb = pk[i] & 0x3FFu, size = (pk[i] >> 10) & 0x7FFu, r = pk[i] >> 21;
-            const bool valid = (uint32_t)(i * 64 + lane) < len;
-            uint32_t o = valid ? sb + r : (uint32_t)CAP;  // invalid items: the sink
-            any |= valid && size > small && !last;        // re-listed: ordered by the next round
-            if (valid && size > 1 && size <= small && !last) {
-                uint32_t cnt = 0;
-                if (cmpst) {
-                    const uint64_t me = ((key[i] & xm) << 10) | (sb + r);
-                    for (uint32_t j0 = 0; j0 < size; j0 += 4) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) cnt += s_k[sb + j0 + u] < me;
-                    }
-                } else {  // low bits; ties by slot
-                    const uint64_t me = key[i] & lowm;
-                    uint32_t lt = 0, eq = 0;
-                    for (uint32_t j0 = 0; j0 < size; j0 += 4) {
-                        uint64_t x[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) x[u] = s_k[sb + j0 + u];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const uint32_t j = j0 + u;
-                            lt += (j < size) & (x[u] < me);
-                            eq += (j < r) & (x[u] == me);
-                        }
-                    }
-                    cnt = lt + eq;
-                }
-                o = sb + cnt;
-            }
-            pk[i] = o;
-        }
-        const bool relist = __ballot(any) != 0;
-        if (relist) {  // (rare) one entry per re-listed sub-bucket, from its first element
-#pragma unroll
-            for (int i = 0; i < I; ++i) {
-                uint32_t size = 0, at = 0;
-                if (i < live && (uint32_t)(i * 64 + lane) < len) {
-                    const uint32_t d = dg_of(key[i], dd);
-                    const uint32_t sb = s_cnt[d];
-                    size = s_cnt[d + 1] - sb;
-                    at = pk[i];
-                    if (size <= small || last || at != sb) size = 0;
-                }
-                route((uint32_t)st + at, size, hi + R, B, 0, false, *Lp, ctr, lane);
-            }
-        }
-        // 5. stage at the final slots (after every rank-by-count read of s_k: in order)
-#pragma unroll
-        for (int i = 0; i < I; ++i) {
-            if (i >= live) continue;
-            s_k[pk[i]] = key[i];
-            s_v[pk[i]] = val[i];
-        }
-        // the next bucket's raw elements (after the last: this one again -- a static count): its
-        // keys and starts are staged, so their registers take the loads, which fly during the
-        // write-back (loading at the top of the bucket instead kept two buckets in registers:
-        // 4 waves per SIMD, measured 22.2 against 20.3 ms at C3)
-        wave_load<I>(en, pfn, lane, k0, k1, v0, v1, cnd, a, b);
-        // 6. write-back: contiguous; group-head flag = the key differs from its predecessor (a
-        // bucket starts a group; re-listed elements get provisional flags).  Items that may be
-        // empty first, skipped when they are; then the MINLIVE items every bucket of the class
-        // fills (its buckets hold more than CAP / 2 elements), unconditionally: the compiler then
-        // knows at least 3 MINLIVE stores follow the next bucket's loads, and the next iteration
-        // waits for those loads without draining them (a branch around every item's stores
-        // drained all; stores for empty items cost more than the drain)
-        const bool wk = WK || relist;
-#pragma unroll
-        for (int ii = 0; ii < I; ++ii) {
-            const int i = ii < I - MINLIVE ? MINLIVE + ii : ii - (I - MINLIVE);
-            if (i >= MINLIVE && i >= live) continue;
-            const uint32_t j = min((uint32_t)(i * 64 + lane), len - 1);
-            const uint64_t kj = s_k[j], kp = s_k[j > 0 ? j - 1 : 0];
-            const uint32_t vj = s_v[j];
-            if (wk) gmem(k0)[st + j] = kj;
-            gmem(v0)[st + j] = vj;
-            gmem(heads)[st + j] = (j == 0 || kj != kp) ? 1 : 0;
-        }
-        idx += lstep;
-        if (idx >= lend) break;
-        e = en;
-        pf = pfn;
-        en = enn;
-        pfn = pfnn;
-    }
-}
-
-// one round's lists, copied to device memory for the wave kernels
-__global__ void lists_store_kernel(Lists L, Lists *__restrict__ dst) { *dst = L; }
-
-// Buckets of <= kTiny elements (mostly from the tie groups of multi-word keys): one thread per
-// bucket, stable rank-by-count over the full word (ties: load order = start order), write-back of
-// starts and head flags to buffer 0.
-__global__ __launch_bounds__(256) void msd_tiny_kernel(const uint2 *__restrict__ list, uint32_t count,
-                                                       uint64_t *k0, uint32_t *v0, const uint64_t *k1,
-                                                       const uint32_t *v1, uint8_t *__restrict__ heads, int wkeys,
-                                                       CompactIn ci, int B) {
-    const uint32_t idx = blockIdx.x * 256 + threadIdx.x;
-    const bool live = idx < count;
-    const uint2 e = live ? list[idx] : make_uint2(0, 1u << 8);
-    const uint64_t st = e.x;
-    const uint32_t len = e.y >> 8;
-    const uint64_t *sk = (e.y & 1) ? k1 : k0;
-    const uint32_t *sv = (e.y & 1) ? v1 : v0;
-    uint64_t key[kTiny];
-    uint32_t val[kTiny];
-    const uint64_t pf = live && ci.pref ? ci.pref[idx] : 0;
-    const int ehi = (e.y >> 1) & 127;
-#pragma unroll
-    for (int j = 0; j < kTiny; ++j) {
-        const uint64_t at = st + min((uint32_t)j, len - 1);
-        const uint64_t x = live ? sk[at] : 0;
-        key[j] = (pf & kCompact) ? compact_key(pf, ehi, B, ci.nd[at], (uint32_t)(x >> 32)) : x;
-        val[j] = !live ? 0 : (pf & kCompact) ? (uint32_t)x : sv[at];
-    }
-    uint32_t out[kTiny];
-    bool hd[kTiny];
-#pragma unroll
-    for (int j = 0; j < kTiny; ++j) {
-        uint32_t lt = 0, eq = 0;
-#pragma unroll
-        for (int i = 0; i < kTiny; ++i) {
-            lt += (uint32_t)i < len && key[i] < key[j];
-            eq += i < j && key[i] == key[j];
-        }
-        out[j] = lt + eq;
-        hd[j] = eq == 0;
-    }
-    if (!live) return;
-#pragma unroll
-    for (int j = 0; j < kTiny; ++j) {
-        if ((uint32_t)j >= len) break;
-        v0[st + out[j]] = val[j];
-        if (wkeys) k0[st + out[j]] = key[j];
-        heads[st + out[j]] = hd[j] ? 1 : 0;
-    }
-}
-
-// Multi-word keys: the groups of >= 2 equal earlier words, from the head flags of the order so far.
-// The first and last element of every such group, in two light passes over the head flags (no
-// flag arrays): COUNT writes per 8192-element tile the numbers of group firsts and lasts; after
-// their scans, STORE writes the indices from the tile's offsets (thread t owns elements
-// 32 t .. 32 t + 31 of the tile, so thread order = index order).
-constexpr int kTieTile = 8192;
-
-template <bool STORE>
-__global__ __launch_bounds__(256) void tie_bounds_kernel(const uint8_t *__restrict__ heads, uint64_t n,
-                                                         uint32_t *__restrict__ cnt_f, uint32_t *__restrict__ cnt_l,
-                                                         const uint32_t *__restrict__ off_f,
-                                                         const uint32_t *__restrict__ off_l,
-                                                         uint32_t *__restrict__ first, uint32_t *__restrict__ last) {
-    __shared__ uint32_t s_w[2][4];
-    const uint64_t i0 = (uint64_t)blockIdx.x * kTieTile + threadIdx.x * 32;
-    uint32_t mf = 0, ml = 0;
-    if (i0 < n) {
-        // 33 head flags from i0 (past n reads as a head: the group ends there)
-        uint32_t hb = 0;
-        if (i0 + 33 <= n) {
-            const uint4 *h4 = reinterpret_cast<const uint4 *>(heads + i0);  // i0 % 32 == 0
-            const uint4 a = h4[0], b = h4[1];
-            const uint32_t wv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int q = 0; q < 32; ++q) hb |= (((wv[q >> 2] >> (8 * (q & 3))) & 0xFFu) != 0 ? 1u : 0u) << q;
-            const bool h32 = heads[i0 + 32] != 0;
-            const uint32_t nxt = (hb >> 1) | ((h32 ? 1u : 0u) << 31);  // bit q: element i0 + q + 1 is a head
-            mf = hb & ~nxt;
-            ml = ~hb & nxt;
-        } else {
-            for (int q = 0; q < 32 && i0 + q < n; ++q) {
-                const bool h = heads[i0 + q] != 0, hn = i0 + q + 1 >= n || heads[i0 + q + 1] != 0;
-                mf |= (h && !hn ? 1u : 0u) << q;
-                ml |= (!h && hn ? 1u : 0u) << q;
-            }
-        }
-    }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cf = (uint32_t)__popc(mf), cl = (uint32_t)__popc(ml);
-    uint32_t inf = cf, inl = cl;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t yf = __shfl_up(inf, o), yl = __shfl_up(inl, o);
-        if (lane >= o) {
-            inf += yf;
-            inl += yl;
-        }
-    }
-    if (lane == 63) {
-        s_w[0][wave] = inf;
-        s_w[1][wave] = inl;
-    }
-    __syncthreads();
-    if (!STORE) {
-        if (threadIdx.x == 0) {
-            cnt_f[blockIdx.x] = s_w[0][0] + s_w[0][1] + s_w[0][2] + s_w[0][3];
-            cnt_l[blockIdx.x] = s_w[1][0] + s_w[1][1] + s_w[1][2] + s_w[1][3];
-        }
-        return;
-    }
-    uint32_t of = off_f[blockIdx.x] + inf - cf, ol = off_l[blockIdx.x] + inl - cl;
-    for (uint32_t w = 0; w < wave; ++w) {
-        of += s_w[0][w];
-        ol += s_w[1][w];
-    }
-    for (uint32_t m = mf; m; m &= m - 1) first[of++] = (uint32_t)(i0 + __ffs(m) - 1);
-    for (uint32_t m = ml; m; m &= m - 1) last[ol++] = (uint32_t)(i0 + __ffs(m) - 1);
-}
-
-__global__ __launch_bounds__(256) void tie_run_lengths_kernel(const uint32_t *__restrict__ first,
-                                                              uint32_t *__restrict__ last_to_len, uint64_t ng) {
-    for (uint64_t g = blockIdx.x * 256ull + threadIdx.x; g < ng; g += (uint64_t)gridDim.x * 256)
-        last_to_len[g] = last_to_len[g] - first[g] + 1;
-}
-
-// Key word of symbols [sym0, sym0 + nsym) of the (canonical) k-mer at p, 2-bit codes, from 17
-// aligned dword loads (issued together) instead of one dependent byte load per symbol: the
-// k-mer's codes as a left-aligned 128-bit value F (SWAR per dword), its reverse complement by
-// two revcomp_word calls and a 128-bit shift, the smaller of the two, then the word.  k <= 64.
-__device__ __forceinline__ uint32_t codes4(uint32_t w) {  // 4 bytes -> 8 bits, byte 0 on top
-    uint32_t t = __builtin_bswap32(((w >> 1) ^ (w >> 2)) & 0x03030303u);
-    t = (t | (t >> 6)) & 0x000F000Fu;
-    return (t | (t >> 12)) & 0xFFu;
-}
-
-__device__ __forceinline__ uint64_t tie_word2(const uint8_t *sba, uint32_t p, int k, int sym0, int nsym,
-                                              bool canonical) {
-    // five 16-byte loads from p & ~15 (80 bytes; 17 dword loads made every k-mer 17 scattered
-    // requests: C5's 113 M tie members took 19 ms)
-    const uint4 *w4 = reinterpret_cast<const uint4 *>(sba + (p & ~15u));
-    uint4 q[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) q[j] = w4[j];
-    const uint32_t w[20] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x, q[2].y,
-                            q[2].z, q[2].w, q[3].x, q[3].y, q[3].z, q[3].w, q[4].x, q[4].y, q[4].z, q[4].w};
-    uint64_t c0 = 0, c1 = 0, c2 = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c0 = (c0 << 8) | codes4(w[j]);
-#pragma unroll
-    for (int j = 8; j < 16; ++j) c1 = (c1 << 8) | codes4(w[j]);
-#pragma unroll
-    for (int j = 16; j < 20; ++j) c2 = (c2 << 8) | codes4(w[j]);
-    c2 <<= 32;  // symbols 64 .. 79 of the stream, on top
-    // symbols 0 .. 63 from p: drop the first `off` (< 16) symbols of the stream
-    const int sh = 2 * (int)(p & 15u);
-    uint64_t fh = sh ? (c0 << sh) | (c1 >> (64 - sh)) : c0;
-    uint64_t fl = sh ? (c1 << sh) | (c2 >> (64 - sh)) : c1;
-    if (k < 64) {  // symbols past the k-mer read as 0
-        if (k <= 32) {
-            fh &= k == 32 ? ~0ull : ~(~0ull >> (2 * k));
-            fl = 0;
-        } else {
-            fl &= ~(~0ull >> (2 * (k - 32)));
-        }
-    }
-    if (canonical) {
-        // reverse complement of the 64-symbol value, then shifted left past the (64 - k) pad symbols
-        uint64_t rh = revcomp_word<2>(fl, 32), rl = revcomp_word<2>(fh, 32);
-        const int ps = 2 * (64 - k);
-        if (ps >= 64) {
-            rh = rl << (ps - 64);
-            rl = 0;
-        } else if (ps > 0) {
-            rh = (rh << ps) | (rl >> (64 - ps));
-            rl <<= ps;
-        }
-        if (rh < fh || (rh == fh && rl < fl)) {
-            fh = rh;
-            fl = rl;
-        }
-    }
-    // the word: symbols sym0 .. sym0 + nsym - 1 of (fh, fl)
-    const int b0 = 2 * sym0, nb = 2 * nsym;  // bit offset from the top, width
-    uint64_t x;
-    if (b0 >= 64) x = fl << (b0 - 64);
-    else x = b0 ? (fh << b0) | (fl >> (64 - b0)) : fh;
-    return nb >= 64 ? x : x >> (64 - nb);
-}
-
-// Flat variant of tie_encode_kernel for many groups: tie_members_kernel lists every element in a group
-// of >= 2 (a head flag of 0 at it or at its successor) -- 32 consecutive flags per thread from two
-// 16-byte loads and one byte; COUNT per 8,192-element tile, scan, STORE at the tile's offset (one
-// list append per wave on a global counter serialised 1.5 M atomics at C5: 16 ms) -- and
-// tie_encode_list_kernel gives each listed element its next key word, one element per thread.  (One
-// thread per element with a byte load per flag kept too few bytes in flight: 9.2 ms for C5's 3.1e9
-// flags; 32 flags per thread with the members encoded in place serialised the lanes of the long
-// runs of members a repeat leaves in the sorted order: 7.6 ms.)
-template <bool STORE>
-__global__ __launch_bounds__(256) void tie_members_kernel(const uint8_t *__restrict__ heads, uint64_t n,
-                                                          uint32_t *__restrict__ cnt, const uint32_t *__restrict__ off,
-                                                          uint32_t *__restrict__ list) {
-    __shared__ uint32_t s_m[4][64 * 32];  // per wave: its members, in element order
-    __shared__ uint32_t s_w[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t i0 = (uint64_t)blockIdx.x * kTieTile + threadIdx.x * 32;  // (as tie_bounds_kernel)
-    uint32_t mem = 0;
-    if (i0 + 33 <= n) {
-        const uint4 *h4 = reinterpret_cast<const uint4 *>(heads + i0);  // i0 % 32 == 0
-        const uint4 a = h4[0], b = h4[1];
-        const uint32_t wv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        uint32_t hb = 0;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) hb |= (((wv[q >> 2] >> (8 * (q & 3))) & 0xFFu) != 0 ? 1u : 0u) << q;
-        const uint32_t nxt = (hb >> 1) | ((heads[i0 + 32] != 0 ? 1u : 0u) << 31);  // bit q: i0 + q + 1 is a head
-        mem = ~hb | ~nxt;
-    } else if (i0 < n) {
-        for (int q = 0; q < 32 && i0 + q < n; ++q) {
-            const uint64_t i = i0 + q;
-            mem |= (heads[i] == 0 || (i + 1 < n && heads[i + 1] == 0) ? 1u : 0u) << q;
-        }
-    }
-    const uint32_t c = (uint32_t)__popc(mem);
-    const uint32_t incl = wave_incl_scan(c);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    if (!STORE) {
-        if (threadIdx.x == 0) cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        return;
-    }
-    uint32_t base = off[blockIdx.x];
-    for (uint32_t w = 0; w < wave; ++w) base += s_w[w];
-    const uint32_t tot = s_w[wave];
-    if (tot == 0) return;  // (wave-uniform)
-    // the wave's members through LDS, stored by consecutive lanes (stored straight from the lanes,
-    // each lane's run of up to 32 made every store instruction 64 scattered partial lines)
-    uint32_t *sm = s_m[wave];
-    uint32_t at = incl - c;
-    for (; mem; mem &= mem - 1) sm[at++] = (uint32_t)(i0 + __ffs(mem) - 1);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    for (uint32_t j = lane; j < tot; j += 64) list[base + j] = sm[j];
-}
-
-template <int BITS>
-__global__ __launch_bounds__(256) void tie_encode_list_kernel(const uint8_t *__restrict__ sba,
-                                                              const uint32_t *__restrict__ list, uint32_t m,
-                                                              const uint32_t *__restrict__ vals,
-                                                              uint64_t *__restrict__ keys, int sym0, int nsym, int k,
-                                                              int canonical) {
-    __shared__ uint8_t s_lut4[256];
-    s_lut4[threadIdx.x] = c_code4_msd[threadIdx.x];
-    __syncthreads();
-    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
-        const uint32_t i = list[j];
-        if (BITS == 2 && k <= 64) {
-            keys[i] = tie_word2(sba, vals[i], k, sym0, nsym, canonical != 0);
-            continue;
-        }
-        const uint8_t *b = sba + vals[i];
-        const bool rc = canonical && canon_is_rc<BITS>(b, k, s_lut4);
-        uint64_t key = 0;
-        for (int t = sym0; t < sym0 + nsym; ++t) key = (key << BITS) | canon_sym<BITS>(b, k, t, rc, s_lut4);
-        keys[i] = key;
-    }
-}
-
-// Next-level buckets whose keys are all equal (a repeat's group of identical k-mers: 250 K
-// elements of (CA)n at C4) would go through every remaining global level without splitting, each
-// with its host round trips.  uniform_flag_kernel marks the buckets holding two different keys
-// (gridDim.y workgroups per bucket); route_uniform_kernel sends the others to the done list.
-__global__ __launch_bounds__(256) void uniform_flag_kernel(const uint32_t *__restrict__ bst,
-                                                           const uint32_t *__restrict__ blen,
-                                                           const uint64_t *__restrict__ keys,
-                                                           uint32_t *__restrict__ mixed,
-                                                           const uint32_t *__restrict__ nb_dev = nullptr,
-                                                           uint32_t *__restrict__ nb_copy = nullptr) {
-    if (nb_copy && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *nb_copy = *nb_dev;
-    if (nb_dev && blockIdx.x >= *nb_dev) return;
-    const uint64_t st = bst[blockIdx.x];
-    const uint32_t len = blen[blockIdx.x];
-    const uint64_t k0 = keys[st];
-    uint64_t acc = 0;
-    for (uint32_t e = blockIdx.y * 256 + threadIdx.x; e < len; e += gridDim.y * 256) acc |= keys[st + e] ^ k0;
-    if (__syncthreads_or(acc != 0) && threadIdx.x == 0) atomicOr(&mixed[blockIdx.x], 1u);
-}
-
-__global__ __launch_bounds__(256) void route_uniform_kernel(const uint32_t *__restrict__ bst,
-                                                            const uint32_t *__restrict__ blen,
-                                                            const uint64_t *__restrict__ bpref, uint32_t nb,
-                                                            const uint32_t *__restrict__ mixed, Lists L, int parity,
-                                                            uint32_t *__restrict__ ctr,
-                                                            unsigned long long *__restrict__ sums, uint32_t tile,
-                                                            uint32_t ctiles, const uint32_t *__restrict__ nb_dev = nullptr) {
-    if (nb_dev) nb = *nb_dev;
-    for (uint32_t b = blockIdx.x * 256 + threadIdx.x; b < nb; b += gridDim.x * 256) {
-        if (mixed[b]) {
-            const uint32_t at = atomicAdd(&ctr[kCtrBig], 1u);
-            put_entry(L, kCtrBig, at, bst[b], blen[b], 0, parity, bpref ? bpref[b] : 0);
-            atomicAdd(&sums[kCtrBig], (unsigned long long)blen[b]);
-            atomicAdd(&sums[kSumTiles], (unsigned long long)tiles_of(blen[b], tile));
-            atomicAdd(&sums[kSumChunks], (unsigned long long)chunks_of(blen[b], tile, ctiles));
-        } else {
-            put_entry(L, kCtrDone, atomicAdd(&ctr[kCtrDone], 1u), bst[b], blen[b], 0, parity);
-        }
-    }
-}
-
-// sub-buckets whose key bits are exhausted: in order already (copied to buffer 0 if needed);
-// all keys equal, so the only head is the first element (gridDim.y workgroups per bucket)
-__global__ __launch_bounds__(256) void done_copy_kernel(const uint32_t *__restrict__ dn_start,
-                                                        const uint32_t *__restrict__ dn_len,
-                                                        const uint8_t *__restrict__ dn_par, const uint32_t *__restrict__ v1,
-                                                        uint32_t *__restrict__ v0, const uint64_t *__restrict__ k1,
-                                                        uint64_t *__restrict__ k0, uint8_t *__restrict__ heads) {
-    const uint32_t s = blockIdx.x;
-    const uint64_t st = dn_start[s];
-    const uint32_t len = dn_len[s];
-    const bool copy = dn_par[s];
-    for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < len; i += gridDim.y * 256) {  // keys: final-key sorts
-        if (copy) v0[st + i] = v1[st + i];
-        if (copy && k1) k0[st + i] = k1[st + i];
-        heads[st + i] = i == 0;
-    }
-}
-
-// Multi-word keys: the next phase's key word of every element of a group of equal earlier words
-// (symbols [sym0, sym0 + nsym) of its k-mer, right-aligned).  One wave per group.
-template <int BITS>
-__global__ __launch_bounds__(256) void tie_encode_kernel(const uint8_t *__restrict__ sba,
-                                                         const uint32_t *__restrict__ g_start,
-                                                         const uint32_t *__restrict__ g_len, uint32_t ngroups,
-                                                         const uint32_t *__restrict__ vals, uint64_t *__restrict__ keys,
-                                                         int sym0, int nsym, int k, int canonical) {
-    __shared__ uint8_t s_lut4[256];
-    s_lut4[threadIdx.x] = c_code4_msd[threadIdx.x];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const uint32_t nw = gridDim.x * 4;
-    for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < ngroups; g += nw) {
-        const uint64_t st = g_start[g];
-        const uint32_t len = g_len[g];
-        if (len < 2) continue;
-        for (uint32_t i = lane; i < len; i += 64) {
-            if (BITS == 2 && k <= 64) {
-                keys[st + i] = tie_word2(sba, vals[st + i], k, sym0, nsym, canonical != 0);
-                continue;
-            }
-            const uint8_t *b = sba + vals[st + i];
-            const bool rc = canonical && canon_is_rc<BITS>(b, k, s_lut4);
-            uint64_t key = 0;
-            for (int t = sym0; t < sym0 + nsym; ++t) key = (key << BITS) | canon_sym<BITS>(b, k, t, rc, s_lut4);
-            keys[st + i] = key;
-        }
-    }
-}
+}  // namespace gkm
+
+// the device code, by stage (private to this file; after c_code4_msd, which the kernels read)
+#include "gkm_msd_l0.h"
+#include "gkm_msd_scan.h"
+#include "gkm_msd_lists.h"
+#include "gkm_msd_local.h"
+#include "gkm_msd_ties.h"
+
+namespace gkm {
 
 // ---------------------------------------------------------------------------------------------
 // host driver
@@ -2645,13 +65,6 @@ __global__ __launch_bounds__(256) void tie_encode_kernel(const uint8_t *__restri
 // n = 0 (grid-stride kernels over elements)
 static int grid256_min1(uint64_t n) { return (int)std::max<uint64_t>((n + 255) / 256, 1); }
 static unsigned grid256_cap64k(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
-
-hipError_t scan_u32_exclusive_pub(gk_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *total);
-hipError_t scan_u32_exclusive_pair(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
-                                   uint32_t *out2, uint64_t n, uint64_t *total1, uint64_t *total2);
-hipError_t scan_u32_exclusive_pair_launch(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
-                                          uint32_t *out2, uint64_t n);
-hipError_t select_flags(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint64_t *count);
 
 // grow a device array to hold `need` entries, keeping the first `keep` entries
 template <typename T>
@@ -2700,6 +113,14 @@ static unsigned resident_per_cu(gk_ctx *c, const void *fn, int threads) {
 
 // tuning only (A/B runs): GKM_NO_COMPACT=1 keeps 64-bit keys in every level's output
 static bool no_compact() { return opt("GKM_NO_COMPACT") != nullptr; }  // (read per level: tests flip it)
+
+// (the transfer's resident copy: stops at every non-ACGT byte, pack2_word<true>)
+hipError_t launch_pack2(const uint8_t *from, uint64_t nwords, uint64_t *code, uint32_t *dol, hipStream_t s) {
+    if (nwords == 0) return hipSuccess;
+    hipLaunchKernelGGL(pack2_kernel<true>, dim3((unsigned)std::min<uint64_t>((nwords + 255) / 256, 65536)), dim3(256),
+                       0, s, from, nwords, code, dol);
+    return hipGetLastError();
+}
 
 // the packed copy of c->sba (pack2_kernel) over the whole padded array, for ACGT sequences: only
 // where the transfer left no resident packed copy and the pass needs one (the starts-only shard
@@ -4219,22 +1640,6 @@ int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks) {
     rc = d.first_level_from_pieces(c->keys[1], c->vals[1], poff.data(), plen.data(), pb.data(),
                                    (uint32_t)poff.size(), 1, d.width(0));
     return d.run_from(rc, 2, d.width(0) + d.width(1), 0);
-}
-
-// starts-only shards (GK_SHARD_STARTS_ONLY): key of the k-mer at every received start from the 2-bit
-// packed copy (B <= 64 bits: the first word), and its next-level digit byte
-__global__ __launch_bounds__(256) void keys_from_starts_kernel(const uint64_t *__restrict__ pk,
-                                                                const uint32_t *__restrict__ vin, uint64_t n, int B,
-                                                                Dig dn, uint64_t *__restrict__ kout,
-                                                                uint8_t *__restrict__ nd) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t s = vin[i], q = s >> 5, sh = (s & 31) * 2;
-        const uint64_t A = pk[q];
-        const uint64_t T = sh ? (A << sh) | (pk[q + 1] >> (64 - sh)) : A;
-        const uint64_t key = T >> (64 - B);
-        kout[i] = key;
-        nd[i] = (uint8_t)dg_of(key, dn);
-    }
 }
 
 // multi-GPU send side: k-mers starting in [lo, hi) partitioned by their top kGR key bits

@@ -1,6 +1,6 @@
 // gkm_partition.h -- stable one-digit partition of (64-bit key, uint32 start) tiles, gfx950.
 //
-// Shared by the MSD sort (gkm_msd.hip) and the timing tool (tools/radix_bench.hip), so the tool
+// Shared by the MSD sort (gkm_msd.hip, gkm_msd_*.h) and the timing tool (tools/radix_bench.hip), so the tool
 // measures the production kernels.  MODE != 0 variants exist for timing experiments only and
 // produce wrong output: 1 = no global stores, 2 = scatter straight from registers (no LDS staging).
 #pragma once
@@ -529,7 +529,7 @@ __device__ __forceinline__ void pipe_store(int g, Dig d, const uint64_t *s_keys,
 
 // INP (input format): 0 = (key, start); 1 = packed pairs (a MODE 5 level's output: kin[] + in16[],
 // key bits below the sorted ones); 2 = packed pairs below a digit byte (the packed L0's output,
-// gkm_msd.hip: nd.in8[] holds the top 8 of the unsorted key bits, kin[] the rest above the start's
+// gkm_msd_l0.h: nd.in8[] holds the top 8 of the unsorted key bits, kin[] the rest above the start's
 // high bits, in16[] the start's low bits).  Only a compact (MODE 4) or packed-pair output, which
 // never store the sorted bits, may read packed input.
 template <int T, int I, int R = 8, int MODE = 0, bool ND = false, int PRE_ = 0, int INP = 0>

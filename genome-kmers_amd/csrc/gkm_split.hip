@@ -3,7 +3,7 @@
 // A 4-bit key spends half its bits on an alphabet the data barely uses: with 16 symbols per word
 // the first MSD word of a 31-mer covers 16 bases, most k-mers tie on it, and every 8-bit digit
 // holds only ~25 live values of 256.  Here the k-mers are split by class:
-//   A  every base in A/C/G/T   -> the 2-bit MSD sort (gkm_msd.hip, acgt_only L0): the C3 speed
+//   A  every base in A/C/G/T   -> the 2-bit MSD sort (gkm_msd.hip, acgt_only L0: gkm_msd_l0.h): the C3 speed
 //   B  some other IUPAC letter -> 4-bit keys, LSD radix sort of the (few) B starts
 // and the two sorted runs are merged.  No A k-mer equals a B k-mer, so the merge is a pure
 // interleave: each B group (run of equal B k-mers) lands before the first A k-mer greater than
@@ -21,10 +21,6 @@
 #include "gkm_swar.h"
 
 namespace gkm {
-
-hipError_t scan_u32_exclusive_pub(gk_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *total);
-hipError_t scan_u32_exclusive_pair(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
-                                   uint32_t *out2, uint64_t n, uint64_t *total1, uint64_t *total2);
 
 __constant__ uint8_t c_code4_split[256];
 __constant__ uint8_t c_comp_split[256];  // the reference's complement (sequence_collection.py:402-433)

@@ -1,4 +1,4 @@
-// SWAR helpers over 8 sequence bytes (gkm_msd.hip's L0 packing, gkm_split.hip's class-B flags)
+// SWAR helpers over 8 sequence bytes (gkm_msd_l0.h's L0 packing, gkm_split.hip's class-B flags)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,7 +106,7 @@ __device__ __forceinline__ void key_from_2bit(uint64_t hi, uint64_t lo, int k, u
     }
 }
 
-// One word of the 2-bit packed sequence layout (gkm_msd.hip pack2_kernel, the L0 kernels' LDS
+// One word of the 2-bit packed sequence layout (gkm_msd_l0.h pack2_kernel, the L0 kernels' LDS
 // tiles): 32 bytes from p (16-byte aligned) -> their 2-bit codes (A0 C1 G2 T3, position 0 in the
 // most significant pair; other bytes get some code) and their '$' flags (position 0 in bit 31)
 // NONACGT: the flags mark every byte other than A/C/G/T ('$' included) -- the stops of the class-A

@@ -2,7 +2,7 @@
 run of one non-ACGT letter, a single IUPAC letter or the end of the array placed around a tile edge
 on purpose; tests/test_edgegen.py pins where) through every L0 path, bit-exact against the CPU oracle.
 
-Tiles: 24,576 positions in the L0 count and partition kernels (gkm_msd.hip kP0Tile), 18,432 in the
+Tiles: 24,576 positions in the L0 count and partition kernels (gkm_msd_l0.h kP0Tile), 18,432 in the
 wide L0, 8,192 in the split sort's class-B flag pass (gkm_split.hip kFlagTile), 4,096 in the
 key-range select; every builder is called with the tile of the kernel under test.  Each test is one
 (path, k, builder) and loops over the builder's arrays, a fresh engine per array; the array's label
@@ -127,7 +127,7 @@ def sort_and_check(eng, r, k, canonical, acgt, tag, timers=None):
 # path -> (tile, k's, library options, packed transfer)
 FORWARD_PATHS = {
     # k = 3, 4: keys narrower than the 7-bit L0 digit; 55, 56 | 57: win8_keep's stop-window switch
-    # (gkm_msd.hip, a.symbols <= 56); 32 | 33 and 63, 64: the ends of the first and second key word
+    # (gkm_msd_l0.h, a.symbols <= 56); 32 | 33 and 63, 64: the ends of the first and second key word
     "default": (T_L0, [3, 4, 8, 31, 32, 33, 55, 56, 57, 63, 64], {}, False),
     # the 11-byte packed L0 output, read back by a pair level (l1_pairs) or expanded (l1_plain)
     "p88-l1_pairs": (T_L0, [24, 31, 32], {"GKM_TEST_P88": "1", "GKM_TEST_PAIRS": "1"}, False),
