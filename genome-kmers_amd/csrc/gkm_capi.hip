@@ -49,6 +49,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_LOOKUP_PATH", false},     {"GKM_LOOKUP_CHUNK", false},    {"GKM_LOOKUP_DIR", false},
     // gk_lookup_mismatch (gkm_mismatch.hip): forced path (bytes | keys), queries per launch
     {"GKM_MISMATCH_PATH", false},   {"GKM_MISMATCH_CHUNK", false},
+    // gk_join (gkm_join.hip): forced path (bytes | keys)
+    {"GKM_JOIN_PATH", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)

@@ -865,6 +865,7 @@ extern "C" int gk_unique_counts(gk_ctx *c, uint64_t *n_unique) {
     if (!c) return GK_E_ARG;
     pre_drop(c);  // (the k-mer buffers: a prefetched L0 does not survive)
     if (!c->sorted || !c->keys_valid) return fail(c, GK_E_STATE, "unique counts need a sorted k-mer set");
+    if (!c->unique_valid) c->join_valid = false;  // a dropped view is rebuilt: gk_join's result went with it
     const int64_t kl = c->sort_len == 0 ? -1 : (int64_t)c->sort_len;
     uint64_t G = 0;
     if (c->heads_valid && !c->keys_are_ranks && c->spec.lenbits == 0 && kl == c->spec.symbols) {

@@ -155,6 +155,12 @@ struct gk_ctx {
     uint64_t n_unique = 0;
     bool unique_valid = false;
 
+    // gk_join's result for this context as side A (gkm_join.hip; scratch "join_first" / "join_count":
+    // uint32[join_n], aligned with the unique view): valid while join_valid && unique_valid, so it is
+    // dropped wherever unique_valid is; gk_unique_counts clears join_valid when it rebuilds a dropped view
+    bool join_valid = false;
+    uint64_t join_n = 0;
+
     // gk_lookup's prefix directory over keys[cur] (gkm_lookup.hip; scratch "lookup_dir"): built by the
     // first key-path lookup after a sort, dropped wherever sorted / keys_valid / heads_valid are reset
     bool lookup_dir_valid = false;

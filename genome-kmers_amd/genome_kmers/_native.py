@@ -58,17 +58,25 @@ EXPORTED = (
     "gk_shard_sort_range_b", "gk_rank_mode", "gk_reference_random_bases",
     "gk_copy_sequence", "gk_sort_hint", "gk_resident_packed", "gk_set_option",
     "gk_lookup", "gk_copy_strand_range", "gk_lookup_mismatch",
+    "gk_join", "gk_copy_join", "gk_device_join", "gk_join_mask",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
 SORT_QUICKSORT_ORDER = 2  # GK_SORT_QUICKSORT_ORDER
 SHARD_STARTS_ONLY = 4  # GK_SHARD_STARTS_ONLY
 MISMATCH_BOTH_STRANDS = 1  # GK_MISMATCH_BOTH_STRANDS
+JOIN_KEEP_ABSENT = 1  # GK_JOIN_KEEP_ABSENT
+JOIN_KEEP_PRESENT = 2  # GK_JOIN_KEEP_PRESENT
 
 
 class GkFilter(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("p0", ctypes.c_int64),
                 ("p1", ctypes.c_int64), ("p2", ctypes.c_int64)]
+
+
+class GkJoinStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_distinct_a", "n_distinct_b", "n_shared", "occ_a_shared",
+                                                     "occ_b_shared", "occ_min")]
 
 
 class GkError(RuntimeError):
@@ -157,6 +165,10 @@ _SIGS = {
     "gk_lookup_mismatch": ([_P, _U8P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U64P, _U32P,
                             _U64P, _U8P, _U8P, ctypes.c_uint64, _U64P], ctypes.c_int),
     "gk_copy_strand_range": ([_P, ctypes.c_uint64, _U8P, ctypes.c_uint64], ctypes.c_int),
+    "gk_join": ([_P, _P, ctypes.c_uint32, ctypes.POINTER(GkJoinStats)], ctypes.c_int),
+    "gk_copy_join": ([_P, _U64P, _U32P, ctypes.c_uint64], ctypes.c_int),
+    "gk_device_join": ([_P, ctypes.POINTER(_P), ctypes.POINTER(_P), _U64P], ctypes.c_int),
+    "gk_join_mask": ([_P, ctypes.c_int], ctypes.c_int),
 }
 
 
@@ -582,6 +594,32 @@ class Engine:
         out = np.empty(count, dtype=np.uint8)
         self._check(self.lib.gk_copy_strand_range(self.ctx, int(offset), _ptr(out, ctypes.c_uint8), int(count)))
         return out
+
+    # ---- two genomes (gk_join) -----------------------------------------------------------------
+    def join(self, other: "Engine") -> dict:
+        """Look every distinct k-mer of this engine's sorted order up in ``other``'s (gk_join); the six
+        sums of gk_join_stats as a dict.  The result stays on the device (join_result, join_mask)."""
+        if not isinstance(other, Engine):
+            raise TypeError(f"join needs an Engine (got {type(other).__name__})")
+        st = GkJoinStats()
+        self._check(self.lib.gk_join(self.ctx, other.ctx, 0, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in GkJoinStats._fields_}
+
+    def join_result(self):
+        """(b_first uint64[u], b_count uint32[u]) of the last join, aligned with unique_counts()
+        (gk_device_join for the length, gk_copy_join)."""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.gk_device_join(self.ctx, None, None, ctypes.byref(n)))
+        first = np.empty(n.value, dtype=np.uint64)
+        count = np.empty(n.value, dtype=np.uint32)
+        self._check(self.lib.gk_copy_join(self.ctx, _ptr(first, ctypes.c_uint64), _ptr(count, ctypes.c_uint32),
+                                          n.value))
+        return first, count
+
+    def join_mask(self, keep: int):
+        """The filter mask of FILTER_MASK written on the device from the last join (gk_join_mask):
+        keep = JOIN_KEEP_ABSENT or JOIN_KEEP_PRESENT."""
+        self._check(self.lib.gk_join_mask(self.ctx, int(keep)))
 
     # ---- multi-GPU shards (genome_kmers.distributed) ------------------------------------------
     def shard_bucket_bits(self) -> int:

@@ -53,6 +53,38 @@ class _DeviceFilter:
         return _native.GkFilter(self.kind, 0, *self.params)
 
 
+class _JoinFilter:
+    """Kmers.absent_from / Kmers.present_in: keep the k-mers of ``owner`` that are absent from /
+    present in ``other``.  It has no host form: the device writes the mask from the join of the two
+    sorted indexes (gk_join, gk_join_mask), so it serves ``get_kmers`` / ``get_kmer_count`` /
+    ``get_kmer_group_counts`` of the Kmers that made it, at ``kmer_len == max_kmer_len``."""
+
+    def __init__(self, owner: "Kmers", other: "Kmers", keep: int, name: str):
+        self.owner = owner
+        self.other = other
+        self.keep = keep
+        self.name = name
+
+    def __call__(self, sba, sba_strand, kmer_sba_start_idx):
+        raise TypeError(f"the filter of Kmers.{self.name} cannot be called as (sba, sba_strand, kmer_sba_start_idx): "
+                        "it compares two sorted indexes on the device; pass it as kmer_filter_func to get_kmers, "
+                        "get_kmer_count or get_kmer_group_counts of the Kmers that made it")
+
+    def device_spec(self, engine: "_native.Engine", owner, kmer_len) -> _native.GkFilter:
+        if owner is None:
+            raise ValueError(f"the filter of Kmers.{self.name} belongs to a Kmers object: the array-level functions "
+                             "(get_kmer_group_size_hist, kmer_info_by_group_generator) cannot evaluate it")
+        if owner is not self.owner:
+            raise ValueError(f"the filter of Kmers.{self.name} was made by another Kmers object: a filter of "
+                             "a.absent_from(b) / a.present_in(b) filters the k-mers of a only")
+        if kmer_len != owner.max_kmer_len:
+            raise ValueError(f"the filter of Kmers.{self.name} compares k-mers at max_kmer_len ({owner.max_kmer_len}) "
+                             f"only (kmer_len = {kmer_len})")
+        owner._join(self.other, self.name)
+        engine.join_mask(self.keep)
+        return _native.GkFilter(_native.FILTER_MASK, 0, 0, 0, 0)
+
+
 def _keep_all(sba, sba_strand, kmer_sba_start_idx):
     return True
 
@@ -266,11 +298,16 @@ def _filter_error(ferr: int, sba_idx: int, filt) -> Exception:
     return RuntimeError(f"device filter error {ferr} at sba index {sba_idx}")
 
 
-def _device_filter(engine: "_native.Engine", filt, sba, sba_strand, starts_fn) -> _native.GkFilter:
+def _device_filter(engine: "_native.Engine", filt, sba, sba_strand, starts_fn, owner=None,
+                   kmer_len=None) -> _native.GkFilter:
     """gk_filter for a built-in filter; a custom Python callable is evaluated once per k-mer on the
-    host (it is user code) into a mask that the device consumes."""
+    host (it is user code) into a mask that the device consumes.  A filter of Kmers.absent_from /
+    present_in (``owner``: the Kmers whose method is filtering, at ``kmer_len``) runs the join and has
+    the device write the mask."""
     if isinstance(filt, _DeviceFilter):
         return filt.gk_filter()
+    if isinstance(filt, _JoinFilter):
+        return filt.device_spec(engine, owner, kmer_len)
     if not callable(filt):
         raise TypeError("kmer_filter_func must be callable")
     starts = starts_fn()
@@ -578,9 +615,9 @@ class Kmers:
             if yield_first_n is not None:
                 raise ValueError(_UNSORTED_GROUP_MSG.format(name="yield_first_n", value=yield_first_n))
 
-    def _filter_spec(self, filt):
+    def _filter_spec(self, filt, kmer_len):
         return _device_filter(self._engine, filt, self.seq_coll.forward_sba, self.seq_coll.strands_loaded(),
-                              lambda: self.kmer_sba_start_indices)
+                              lambda: self.kmer_sba_start_indices, owner=self, kmer_len=kmer_len)
 
     # ---- queries (kmers.py:869-1178) ---------------------------------------------------------
     def get_kmers(self, kmer_len: Union[int, None], one_based_seq_index: bool = False,
@@ -599,7 +636,7 @@ class Kmers:
         self._sync_device()
         if self._engine.n == 0:
             return
-        filt = self._filter_spec(kmer_filter_func)
+        filt = self._filter_spec(kmer_filter_func, kmer_len)
         try:
             nums, yielded, totals = self._engine.group_members(self._is_sorted, kmer_len, filt, min_group_size,
                                                                max_group_size, yield_first_n)
@@ -687,7 +724,7 @@ class Kmers:
         self._sync_device()
         if self._engine.n == 0:
             return np.zeros(max_counts_bin + 1, dtype=np.int64), 0
-        filt = self._filter_spec(kmer_filter_func)
+        filt = self._filter_spec(kmer_filter_func, kmer_len)
         try:
             return self._engine.group_hist(self._is_sorted, kmer_len, filt, min_group_size, max_group_size,
                                            max_counts_bin)
@@ -804,6 +841,66 @@ class Kmers:
         _, _, names, seg, _, _, seq_idx = self._locate_records(nums, one_based_seq_index)
         return [("-" if st else "+", names[sg], sq, mm)
                 for st, sg, sq, mm in zip(strand.tolist(), seg.tolist(), seq_idx.tolist(), mism.tolist())]
+
+    # ---- two genomes (no reference counterpart: the reference holds one genome at a time) ------
+    def _join_checks(self, other, what):
+        """The preconditions of gk_join, checked on the host before any device call."""
+        if not isinstance(other, Kmers):
+            raise ValueError(f"{what} compares two Kmers objects (self: Kmers, other: {type(other).__name__})")
+        if not self._is_sorted or not other._is_sorted:
+            raise AssertionError(f"The kmers must be sorted when calling {what} (self sorted: {self._is_sorted}, "
+                                 f"other sorted: {other._is_sorted})")
+        if self.kmer_source_strand != "forward" or other.kmer_source_strand != "forward":
+            raise ValueError(f"{what} needs kmer_source_strand 'forward' on both sides (self: "
+                             f"{self.kmer_source_strand!r}, other: {other.kmer_source_strand!r})")
+        if self.max_kmer_len is None or self.max_kmer_len != other.max_kmer_len:
+            raise ValueError(f"{what} needs one fixed max_kmer_len on both sides (self: {self.max_kmer_len}, "
+                             f"other: {other.max_kmer_len})")
+        for side, km in (("self", self), ("other", other)):
+            if km.min_kmer_len != km.max_kmer_len:
+                raise ValueError(f"{what} needs min_kmer_len == max_kmer_len, no k-mer cut short by a contig end "
+                                 f"({side}: min_kmer_len = {km.min_kmer_len}, max_kmer_len = {km.max_kmer_len})")
+        if self._canonical != other._canonical:
+            raise ValueError(f"{what} needs both sides sorted the same way, canonical or not (self canonical: "
+                             f"{self._canonical}, other canonical: {other._canonical})")
+
+    def _join(self, other, what) -> dict:
+        self._join_checks(other, what)
+        self._sync_device()
+        other._sync_device()
+        return self._engine.join(other._engine)
+
+    def count_in(self, other: "Kmers") -> tuple:
+        """``(first, count)`` aligned with ``get_unique_kmers()``: for each distinct k-mer of this
+        sorted index its multiplicity in ``other``'s and the number of ``other``'s sorted k-mers that
+        compare less than it (its insertion point where the count is 0; find's convention), from
+        one join of the two indexes on the GPU (gk_join).  Both sorted, one fixed length
+        (min_kmer_len == max_kmer_len, the same on both sides), both canonical or neither."""
+        self._join(other, "count_in")
+        return self._engine.join_result()
+
+    def compare(self, other: "Kmers") -> dict:
+        """Shared and private k-mers of two sorted indexes (gk_join): the six sums of gk_join_stats
+        (``n_distinct_a``, ``n_distinct_b``, ``n_shared``, ``occ_a_shared``, ``occ_b_shared``,
+        ``occ_min``; a = self), ``jaccard`` = shared / (distinct in either; 0.0 when both are empty)
+        and ``containment`` = shared / distinct in self."""
+        st = self._join(other, "compare")
+        da, db, shared = st["n_distinct_a"], st["n_distinct_b"], st["n_shared"]
+        st["jaccard"] = shared / (da + db - shared) if da + db - shared else 0.0
+        st["containment"] = shared / da if da else 0.0
+        return st
+
+    def absent_from(self, other: "Kmers") -> _JoinFilter:
+        """A ``kmer_filter_func`` for this object's ``get_kmers`` / ``get_kmer_count`` /
+        ``get_kmer_group_counts`` at ``kmer_len == max_kmer_len``: keep the k-mers that do not occur in
+        ``other`` (the join runs when the filter is used, so it sees ``other`` as it is then)."""
+        self._join_checks(other, "absent_from")
+        return _JoinFilter(self, other, _native.JOIN_KEEP_ABSENT, "absent_from")
+
+    def present_in(self, other: "Kmers") -> _JoinFilter:
+        """As ``absent_from``, keeping the k-mers that occur in ``other``."""
+        self._join_checks(other, "present_in")
+        return _JoinFilter(self, other, _native.JOIN_KEEP_PRESENT, "present_in")
 
     def get_encoded_kmers(self) -> np.ndarray:
         """Encoded keys of the sorted k-mers, one row per k-mer."""

@@ -345,6 +345,47 @@ int gk_lookup_mismatch(gk_ctx *ctx, const uint8_t *queries, uint64_t m, uint32_t
                        uint32_t flags, uint64_t *counts, uint32_t *hit_query, uint64_t *hit_kmer_num,
                        uint8_t *hit_mismatches, uint8_t *hit_strand, uint64_t capacity, uint64_t *n_hits);
 
+/* Join of two sorted contexts (no reference routine: the reference holds one genome at a time; equality
+ * and order are its compare_sba_kmers_lexicographically at the common sort length K, kmers.py:306-397,
+ * of the canonical forms -- gkm_canon.h -- after GK_SORT_CANONICAL on both sides).  Every distinct
+ * k-mer of a -- entry u of a's unique view, gk_unique_counts, which gk_join computes on either side
+ * when it is not valid -- is looked up in b: b_count[u] = its multiplicity in b, b_first[u] = the number
+ * of b's sorted k-mers that compare less than it (its insertion point when b_count[u] == 0; gk_lookup's
+ * convention).  The result is aligned with gk_copy_unique(a), stays in context a as device uint32
+ * arrays (a snapshot of b) and is dropped wherever a's unique view is dropped (a sort, new starts, a new
+ * sequence, a group pass).  stats (may be NULL): integer sums, the same on every run and on both paths.
+ * a == b is allowed (b_count == count, b_first == group_start); an empty side gives GK_OK and zeros.
+ * b's stream is synchronised before a's stream reads b's buffers; the work runs on a's stream, which
+ * the call synchronises.  Two paths with the same answers: a streaming merge of the two unique views'
+ * keys when both contexts hold final one-word 2-bit forward keys (A/C/G/T only, K <= 32, forward
+ * order), else one search per distinct k-mer of a over b's sorted starts comparing sequence bytes
+ * (mixed alphabets on either side, K > 32, canonical orders); GKM_JOIN_PATH = bytes | keys
+ * (gk_set_option) forces one, keys where it does not apply: GK_E_UNSUPPORTED.
+ * GK_E_ARG: a null context, contexts on different devices, flags != 0, different sort lengths, one side
+ * canonical and the other not; GK_E_STATE: a side without a sequence or not sorted;
+ * GK_E_UNSUPPORTED: sort length 0 (None), or a side whose min_kmer_len differs from its sort length
+ * (k-mers cut short by a contig end).  Each message names the values. */
+typedef struct gk_join_stats {
+    uint64_t n_distinct_a, n_distinct_b;   /* distinct k-mers of each side                          */
+    uint64_t n_shared;                      /* distinct k-mers present in both                       */
+    uint64_t occ_a_shared, occ_b_shared;    /* occurrences in A, in B, of the shared k-mers          */
+    uint64_t occ_min;                       /* sum over shared k-mers of min(count in A, count in B) */
+} gk_join_stats;
+int gk_join(gk_ctx *a, gk_ctx *b, uint32_t flags, gk_join_stats *stats);
+/* the result of the last gk_join(ctx, ...): copied out (b_first widened as gk_copy_unique's group starts;
+ * n must equal ctx's distinct count, GK_E_ARG otherwise; either array may be NULL), or as device
+ * pointers uint32[*n].  GK_E_STATE without a valid join. */
+int gk_copy_join(gk_ctx *a, uint64_t *b_first, uint32_t *b_count, uint64_t n);
+int gk_device_join(gk_ctx *a, void **b_first, void **b_count, uint64_t *n);
+/* Writes the filter mask of GK_FILTER_MASK on the device (as gk_set_filter_mask would, one byte per
+ * sorted position): 1 where the k-mer at the position is absent from b (GK_JOIN_KEEP_ABSENT) or
+ * present in b (GK_JOIN_KEEP_PRESENT) by the last gk_join, else 0; the cost per position does not
+ * depend on the group's size.  Any other keep: GK_E_ARG; GK_E_STATE without a valid join.  The group
+ * pass that then reads the mask drops the join with the unique view. */
+#define GK_JOIN_KEEP_ABSENT 1
+#define GK_JOIN_KEEP_PRESENT 2
+int gk_join_mask(gk_ctx *a, int keep);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
