@@ -51,6 +51,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_MISMATCH_PATH", false},   {"GKM_MISMATCH_CHUNK", false},
     // gk_join (gkm_join.hip): forced path (bytes | keys)
     {"GKM_JOIN_PATH", false},
+    // gk_screen (gkm_screen.hip): forced path (bytes | keys), bytes of reads per launch
+    {"GKM_SCREEN_PATH", false},     {"GKM_SCREEN_CHUNK", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)

@@ -381,6 +381,9 @@ inline bool lookup_keys_usable(const gk_ctx *c) {
            ks.words == 1 && ks.lenbits == 0 && !ks.canonical && !ks.acgt_only && ks.symbols >= 1 &&
            ks.symbols <= 32 && (uint32_t)ks.symbols == c->sort_len && c->keys[c->cur] != nullptr;
 }
+// the prefix directory over keys[cur] (gkm_lookup.hip; needs lookup_keys_usable), built when it is
+// not valid; c->lookup_dir_bits is its D
+int lookup_build_dir(gk_ctx *c, uint32_t **out);
 
 // group / scan
 hipError_t select_flags(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint64_t *count);

@@ -19,6 +19,7 @@
 #include "gkm_canon.h"
 #include "gkm_internal.h"
 #include "gkm_lookup_host.h"
+#include "gkm_lookup_search.h"
 
 namespace gkm {
 
@@ -99,10 +100,8 @@ __global__ __launch_bounds__(kLookupThreads) void lookup_dir_kernel(const uint64
     }
 }
 
-// keys: n one-word keys of `symbols` 2-bit symbols, right-aligned, ascending.  The
-// q-symbol prefix of a key is key >> shift with shift = 2 (symbols - q) in [0, 62]: no sum that
-// could pass 2^64 (the all-T 32-mer is 2^64 - 1) and no shift by 64.  dir (may be null): the
-// directory of the top D bits above.
+// keys: n one-word keys of `symbols` 2-bit symbols, ascending; dir (may be null): the directory of the
+// top D bits above.  The search itself is key_search (gkm_lookup_search.h), shared with gk_screen.
 __global__ __launch_bounds__(kLookupThreads) void lookup_keys_kernel(
     const uint64_t *__restrict__ keys, uint64_t n, int symbols, const uint32_t *__restrict__ dir, int D,
     const uint8_t *__restrict__ queries, uint64_t m, uint32_t qlen, uint64_t *__restrict__ first,
@@ -112,35 +111,14 @@ __global__ __launch_bounds__(kLookupThreads) void lookup_keys_kernel(
     for (uint64_t i = blockIdx.x * (uint64_t)kLookupThreads + threadIdx.x; i < m;
          i += (uint64_t)gridDim.x * kLookupThreads) {
         const uint8_t *qg = queries + i * qlen;
-        uint64_t prefix = 0;
-        for (uint32_t t = 0; t < qlen; ++t) prefix = (prefix << 2) | canon_code<2>(qg[t], nullptr);
-        uint64_t lo = 0, hi = n;
-        if (dir != nullptr) {
-            if (qb < D) {  // the two entries that bracket the prefix are the answer
-                const uint64_t a = dir[prefix << (D - qb)], b = dir[(prefix + 1) << (D - qb)];
-                first[i] = a;
-                count[i] = (uint32_t)(b - a);
-                continue;
-            }
-            const uint64_t d = prefix >> (qb - D);
-            lo = dir[d];
-            hi = dir[d + 1];
-        }
-        const uint64_t end = hi;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if ((keys[mid] >> shift) < prefix) lo = mid + 1;
-            else hi = mid;
-        }
-        const uint64_t lb = lo;
-        hi = end;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if ((keys[mid] >> shift) <= prefix) lo = mid + 1;
-            else hi = mid;
-        }
-        first[i] = lb;
-        count[i] = (uint32_t)(lo - lb);
+        uint64_t prefix[1] = {0};
+        for (uint32_t t = 0; t < qlen; ++t) prefix[0] = (prefix[0] << 2) | canon_code<2>(qg[t], nullptr);
+        const bool active[1] = {true};
+        uint64_t f[1];
+        uint32_t cnt[1];
+        key_search<1>(keys, n, dir, D, qb, shift, prefix, active, f, cnt);
+        first[i] = f[0];
+        count[i] = cnt[0];
     }
 }
 
@@ -149,7 +127,7 @@ static unsigned lookup_grid(uint64_t items) {
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(g, 1), kLookupMaxBlocks);
 }
 
-static int lookup_build_dir(gk_ctx *c, uint32_t **out) {
+int lookup_build_dir(gk_ctx *c, uint32_t **out) {
     const int D = std::min(kLookupDirBits, 2 * c->spec.symbols);
     const uint64_t entries = (1ull << D) + 1;
     uint32_t *dir;

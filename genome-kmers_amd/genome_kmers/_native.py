@@ -59,6 +59,7 @@ EXPORTED = (
     "gk_copy_sequence", "gk_sort_hint", "gk_resident_packed", "gk_set_option",
     "gk_lookup", "gk_copy_strand_range", "gk_lookup_mismatch",
     "gk_join", "gk_copy_join", "gk_device_join", "gk_join_mask",
+    "gk_screen",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
@@ -67,6 +68,7 @@ SHARD_STARTS_ONLY = 4  # GK_SHARD_STARTS_ONLY
 MISMATCH_BOTH_STRANDS = 1  # GK_MISMATCH_BOTH_STRANDS
 JOIN_KEEP_ABSENT = 1  # GK_JOIN_KEEP_ABSENT
 JOIN_KEEP_PRESENT = 2  # GK_JOIN_KEEP_PRESENT
+SCREEN_BOTH_STRANDS = 1  # GK_SCREEN_BOTH_STRANDS
 
 
 class GkFilter(ctypes.Structure):
@@ -169,6 +171,7 @@ _SIGS = {
     "gk_copy_join": ([_P, _U64P, _U32P, ctypes.c_uint64], ctypes.c_int),
     "gk_device_join": ([_P, ctypes.POINTER(_P), ctypes.POINTER(_P), _U64P], ctypes.c_int),
     "gk_join_mask": ([_P, ctypes.c_int], ctypes.c_int),
+    "gk_screen": ([_P, _U8P, _U64P, ctypes.c_uint64, ctypes.c_uint32, _U32P, _U64P, _U32P], ctypes.c_int),
 }
 
 
@@ -344,6 +347,53 @@ def pack_queries(kmers, kmer_len: int = None) -> np.ndarray:
         raise ValueError(f"k-mer {int(i)} holds the character {chr(int(arr[i, j]))!r}, outside the alphabet "
                          f"{QUERY_ALPHABET.decode()}")
     return arr
+
+
+def pack_sequences(seqs):
+    """The read batch of gk_screen: ``(uint8[total], uint64[nseq + 1])``, the sequences' ASCII bytes
+    back to back and their offsets (sequence j is ``[offsets[j], offsets[j + 1])``).  Host only.
+
+    ``seqs``: one ``str`` / ``bytes`` (a batch of one), a list of them (any lengths, empty ones
+    allowed), or an already packed ``(array, offsets)`` pair, whose offsets must start at 0, never
+    decrease and end at the array's length.  ValueError: such offsets, an entry that is neither str nor
+    bytes, a character outside ABCDGHKMNRSTVWY (upper case; the message names the sequence's index,
+    the offset in it and the character)."""
+    if isinstance(seqs, (str, bytes, bytearray)):
+        seqs = [seqs]
+    if isinstance(seqs, tuple) and len(seqs) == 2 and isinstance(seqs[0], np.ndarray):
+        arr, offsets = seqs
+        if arr.ndim != 1 or arr.dtype != np.uint8:
+            raise ValueError(f"a packed sequence array must be 1-D uint8 (ndim = {arr.ndim}, dtype = {arr.dtype})")
+        arr = np.ascontiguousarray(arr)
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.size == 0 or off.dtype.kind not in "iu" or (off.dtype.kind == "i" and (off < 0).any()):
+            raise ValueError("offsets must be a 1-D array of nseq + 1 non-negative integers")
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off[0] != 0 or off[-1] != arr.size or (off[1:] < off[:-1]).any():
+            raise ValueError(f"offsets must start at 0, never decrease and end at the array's length ({arr.size})")
+    else:
+        parts = []
+        for i, s in enumerate(seqs):
+            if isinstance(s, str):
+                try:
+                    s = s.encode("ascii")
+                except UnicodeEncodeError:
+                    j, bad = next((j, ch) for j, ch in enumerate(s) if ord(ch) > 127)
+                    raise ValueError(f"sequence {i} holds the character {bad!r} at offset {j}, outside the alphabet "
+                                     f"{QUERY_ALPHABET.decode()}") from None
+            elif not isinstance(s, (bytes, bytearray)):
+                raise ValueError(f"sequence {i} is neither str nor bytes ({type(s).__name__})")
+            parts.append(bytes(s))
+        arr = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(p) for p in parts], dtype=np.uint64), out=off[1:])
+    ok = _QUERY_OK[arr]
+    if not ok.all():
+        pos = int(np.argmin(ok))
+        j = int(np.searchsorted(off, pos, side="right")) - 1
+        raise ValueError(f"sequence {j} holds the character {chr(int(arr[pos]))!r} at offset {pos - int(off[j])}, "
+                         f"outside the alphabet {QUERY_ALPHABET.decode()}")
+    return arr, off
 
 
 def device_count() -> int:
@@ -620,6 +670,25 @@ class Engine:
         """The filter mask of FILTER_MASK written on the device from the last join (gk_join_mask):
         keep = JOIN_KEEP_ABSENT or JOIN_KEEP_PRESENT."""
         self._check(self.lib.gk_join_mask(self.ctx, int(keep)))
+
+    # ---- reads against the index (gk_screen) ---------------------------------------------------
+    def screen(self, seqs: np.ndarray, offsets: np.ndarray, both_strands: bool = False, per_window: bool = False):
+        """(n_present uint32[nseq], occurrences uint64[nseq], window_counts uint32[total] or None) of
+        a pack_sequences batch against the sorted order (gk_screen)."""
+        arr = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if arr.ndim != 1 or off.ndim != 1 or off.size == 0:
+            raise ValueError("screen takes a 1-D uint8 array and its nseq + 1 offsets")
+        nseq = off.size - 1
+        n_present = np.zeros(nseq, dtype=np.uint32)
+        occurrences = np.zeros(nseq, dtype=np.uint64)
+        wc = np.zeros(arr.size, dtype=np.uint32) if per_window else None
+        if nseq:
+            self._check(self.lib.gk_screen(self.ctx, _ptr(arr, ctypes.c_uint8), _ptr(off, ctypes.c_uint64), nseq,
+                                           SCREEN_BOTH_STRANDS if both_strands else 0, _ptr(n_present, ctypes.c_uint32),
+                                           _ptr(occurrences, ctypes.c_uint64),
+                                           _ptr(wc, ctypes.c_uint32) if per_window else None))
+        return n_present, occurrences, wc
 
     # ---- multi-GPU shards (genome_kmers.distributed) ------------------------------------------
     def shard_bucket_bits(self) -> int:

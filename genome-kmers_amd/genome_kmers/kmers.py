@@ -22,6 +22,7 @@ as host functions for API compatibility; when a built-in filter or comparator is
 """
 
 import shelve
+from collections import namedtuple
 from pathlib import Path
 from typing import Callable, Generator, Union
 
@@ -31,6 +32,11 @@ from . import _native
 from .sequence_collection import SequenceCollection
 
 DOLLAR = ord("$")
+
+# Kmers.screen's result: per read the number of windows, of windows present in the index and the sum of
+# the windows' counts; with per_window=True also the count per byte position and the reads' offsets
+ScreenResult = namedtuple("ScreenResult", ("n_windows", "n_present", "occurrences", "window_counts", "offsets"),
+                          defaults=(None, None))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -901,6 +907,33 @@ class Kmers:
         """As ``absent_from``, keeping the k-mers that occur in ``other``."""
         self._join_checks(other, "present_in")
         return _JoinFilter(self, other, _native.JOIN_KEEP_PRESENT, "present_in")
+
+    # ---- reads against the index (no reference counterpart) -----------------------------------
+    def screen(self, seqs, both_strands: bool = False, per_window: bool = False) -> ScreenResult:
+        """How much of each read of a batch is in this sorted index, answered on the GPU (gk_screen).
+
+        ``seqs``: one ``str`` / ``bytes`` (a batch of one), a list of them, or a packed
+        ``(array, offsets)`` pair (_native.pack_sequences).  Every window of max_kmer_len bytes inside
+        one read counts what ``find`` would return as ``count`` for it (after sort(canonical=True):
+        for min(window, reverse complement)).  ``both_strands`` on a forward order adds the count of
+        the window's reverse complement (once for a window that is its own); on a canonical order it
+        changes nothing.  Returns ``ScreenResult``: per read ``n_windows`` (uint32, max(0, L - K + 1)),
+        ``n_present`` (uint32, windows with a count above 0) and ``occurrences`` (uint64, the sum of
+        the counts); with ``per_window`` also ``window_counts`` (uint32 per byte of the batch: the
+        count of the window that starts there, 0 where none does) and the reads' ``offsets``."""
+        self._check_forward()
+        if not self._is_sorted:
+            raise AssertionError("The kmers must be sorted when calling screen")
+        if self.max_kmer_len is None:
+            raise ValueError("screen needs a fixed max_kmer_len (the windows' length); max_kmer_len is None")
+        arr, off = _native.pack_sequences(seqs)
+        self._sync_device()
+        n_present, occurrences, wc = self._engine.screen(arr, off, both_strands, per_window)
+        lens = np.diff(off).astype(np.int64)
+        n_windows = np.maximum(lens - (self.max_kmer_len - 1), 0).astype(np.uint32)
+        if per_window:
+            return ScreenResult(n_windows, n_present, occurrences, wc, off)
+        return ScreenResult(n_windows, n_present, occurrences)
 
     def get_encoded_kmers(self) -> np.ndarray:
         """Encoded keys of the sorted k-mers, one row per k-mer."""

@@ -386,6 +386,35 @@ int gk_device_join(gk_ctx *a, void **b_first, void **b_count, uint64_t *n);
 #define GK_JOIN_KEEP_PRESENT 2
 int gk_join_mask(gk_ctx *a, int keep);
 
+/* Screen a batch of reads against the sorted index (no reference routine: the reference offers no
+ * search; a window's count is gk_lookup's, by its compare_sba_kmers_lexicographically, kmers.py:306-397).
+ * seqs: offsets[nseq] ASCII bytes, host memory, the sequences back to back without separators;
+ * sequence j is the bytes [offsets[j], offsets[j + 1]).  offsets: nseq + 1 entries, starting at 0 and
+ * never decreasing (empty sequences are allowed); no sequence is longer than 2^32 - 1 bytes.  The bytes
+ * are letters of the sba alphabet without '$' (gk_lookup's rule).  K is the sort length.
+ * For every window of K bytes that lies inside one sequence, the window's count is exactly what
+ * gk_lookup returns as `count` for those K bytes as a query with qlen = K: after GK_SORT_CANONICAL the
+ * window stands for min(window, reverse complement).  With GK_SCREEN_BOTH_STRANDS on a forward order
+ * the count is count(window) + count(reverse complement of window, the reference's IUPAC complement,
+ * sequence_collection.py:402-433), counted once when the window is its own reverse complement; on a
+ * canonical order the flag changes nothing.
+ * n_present[j] = the number of windows of sequence j with count > 0; occurrences[j] = the sum of the
+ * counts of its windows; window_count (may be NULL, else offsets[nseq] entries): entry p = the count of
+ * the window that starts at byte p, 0 where none starts (the last K - 1 bytes of a sequence, a sequence
+ * shorter than K).  Integer results, the same on every run and on both paths.  A sequence of L bytes
+ * has max(0, L - K + 1) windows.  Each byte crosses to the device once; the windows are formed and the
+ * per-sequence sums taken there.  Synchronises the stream; leaves the sorted order, the unique view
+ * and a join result as they are.
+ * GK_E_STATE: no sequence, or not sorted; GK_E_UNSUPPORTED: sort length 0 (None); GK_E_ARG: a null
+ * context or array, unknown flag bits, offsets that do not start at 0 or decrease, a sequence over
+ * 2^32 - 1 bytes (all checked before any byte of seqs is read); GK_E_ALPHABET: a byte outside the
+ * alphabet (found on the device; the message names the sequence, the offset in it and the byte; the
+ * outputs are then unspecified).  nseq == 0 returns GK_OK and touches nothing; a total length of 0
+ * writes zeros to the per-sequence outputs. */
+#define GK_SCREEN_BOTH_STRANDS 1u
+int gk_screen(gk_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint64_t nseq, uint32_t flags,
+              uint32_t *n_present, uint64_t *occurrences, uint32_t *window_count);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
