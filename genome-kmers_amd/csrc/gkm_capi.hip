@@ -611,8 +611,8 @@ extern "C" void gk_destroy(gk_ctx *c) {
     if (c->pre_stream) hipStreamSynchronize(c->pre_stream);
     xfer_release(c);
     if (c->hpin) hipHostFree(c->hpin);
-    if (c->lookup_pin) hipHostFree(c->lookup_pin);
-    for (hipEvent_t e : c->lookup_ev)
+    if (c->stage_pin) hipHostFree(c->stage_pin);
+    for (hipEvent_t e : c->stage_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->pre_ev) hipEventDestroy(e);
     if (c->pre_done) hipEventDestroy(c->pre_done);

@@ -165,11 +165,12 @@ struct gk_ctx {
     // first key-path lookup after a sort, dropped wherever sorted / keys_valid / heads_valid are reset
     bool lookup_dir_valid = false;
     int lookup_dir_bits = 0;   // D: the directory indexes the top D key bits
-    // gk_lookup's pinned host staging: two slots (queries, first, count of one chunk each), so the
-    // host fills one while the copy engine reads the other; lookup_ev[s]: slot s's results landed
-    uint8_t *lookup_pin = nullptr;
-    uint64_t lookup_pin_cap = 0;
-    hipEvent_t lookup_ev[2] = {nullptr, nullptr};
+    // pinned host staging that gk_lookup and gk_screen share (stage_reserve; both leave it idle when
+    // they return): two slots of one chunk's input and results each, so the host fills one while the
+    // copy engine reads the other; stage_ev[s]: slot s's results landed
+    uint8_t *stage_pin = nullptr;
+    uint64_t stage_pin_cap = 0;
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};
 
     // named, grow-only scratch buffers (MSD sort tables etc.)
     std::map<std::string, std::pair<void *, uint64_t>> scratch;
@@ -361,18 +362,11 @@ __device__ __forceinline__ uint64_t seg_end_of(const uint32_t *__restrict__ seg,
 }
 constexpr uint64_t kMsdKeysMin = 1ull << 20;
 
-// gk_lookup / gk_lookup_mismatch (gkm_lookup.hip, gkm_mismatch.hip)
-// 4-bit symbol code of byte b (gkm_canon.h: '$' and anything else 0, A B C D G H K M N R S T V W Y ->
-// 1..15), computed rather than read from a table in constant memory: each block fills its 256-byte
-// LDS copy once, one byte per thread, so there is no per-device upload to keep track of
-__device__ __forceinline__ uint8_t lookup_code4(uint32_t b) {
-    constexpr char kOrder[] = "ABCDGHKMNRSTVWY";
-    uint8_t code = 0;
-#pragma unroll
-    for (int i = 0; i < 15; ++i)
-        if (b == (uint32_t)kOrder[i]) code = (uint8_t)(i + 1);
-    return code;
-}
+// the query calls: gk_lookup, gk_lookup_mismatch, gk_join, gk_screen (these two: gkm_lookup.hip)
+// the context's pinned staging grown to two slots of slot_bytes (contents not kept), stage_ev created
+int stage_reserve(gk_ctx *c, uint64_t slot_bytes);
+// GK_E_ALPHABET for byte `bad` of a batch of qlen-byte queries
+int fail_alphabet(gk_ctx *c, const uint8_t *queries, uint64_t bad, uint32_t qlen);
 
 // the context holds final one-word 2-bit forward keys in sorted order (no re-encode is triggered)
 inline bool lookup_keys_usable(const gk_ctx *c) {

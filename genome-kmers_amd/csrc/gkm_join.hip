@@ -8,7 +8,7 @@
 // ("Join"):
 //   bytes  one thread per distinct k-mer of A: lower and upper bound over B's sorted starts, comparing
 //          B's sba bytes with A's at its group head in 4-bit symbol codes, the canonical form of both
-//          on canonical orders (gkm_canon.h), as lookup_bytes_kernel does.  Always valid.
+//          on canonical orders: gk_lookup's search (gkm_bytes_search.h).  Always valid.
 //   keys   both contexts hold final one-word 2-bit forward keys of the same K (lookup_keys_usable): a
 //          streaming merge join of the two unique views.  A partition kernel finds the merge-path
 //          split of every tile boundary (gkm_join_host.h: diagonal_split, A first on a tie); a tile
@@ -18,11 +18,10 @@
 // Both reduce the four sums of gk_join_stats over the shared k-mers in integers (LDS atomics per
 // block, one global atomic per block and sum): reproducible whatever the scheduling.
 #include <algorithm>
-#include <cstring>
-
-#include "gkm_canon.h"
+#include "gkm_bytes_search.h"
 #include "gkm_internal.h"
 #include "gkm_join_host.h"
+#include "gkm_query_host.h"
 
 namespace gkm {
 
@@ -56,21 +55,9 @@ __device__ __forceinline__ void join_reduce(const JoinSums &t, unsigned long lon
 // ---------------------------------------------------------------------------------------------
 // byte path
 // ---------------------------------------------------------------------------------------------
-// sign of (B's k-mer at pb) - (A's k-mer at pa) over k symbols in 4-bit codes, the canonical form of
-// both if CANON (rc_a: A's is its reverse complement).  Both k-mers are whole (gk_join refuses a side
-// with k-mers cut short), so no symbol is a '$'.
-template <bool CANON>
-__device__ __forceinline__ int join_cmp(const uint8_t *__restrict__ pb, const uint8_t *__restrict__ pa, bool rc_a,
-                                        int k, const uint8_t *lut4) {
-    const bool rc_b = CANON && canon_is_rc<4>(pb, k, lut4);
-    for (int t = 0; t < k; ++t) {
-        const uint32_t x = CANON ? canon_sym<4>(pb, k, t, rc_b, lut4) : (uint32_t)lut4[pb[t]];
-        const uint32_t y = CANON ? canon_sym<4>(pa, k, t, rc_a, lut4) : (uint32_t)lut4[pa[t]];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return 0;
-}
-
+// bytes_range (gkm_bytes_search.h) over B's sorted starts, the sought k-mer A's at its group head in
+// A's sba: its canonical form if CANON, its strand (rc_a) found once, outside the search.  Both
+// k-mers are whole (gk_join refuses a side with k-mers cut short), so no symbol is a '$'.
 template <bool CANON>
 __global__ __launch_bounds__(kJoinThreads) void join_bytes_kernel(
     const uint8_t *__restrict__ sba_a, const uint32_t *__restrict__ starts_a, const uint32_t *__restrict__ heads_a,
@@ -79,7 +66,7 @@ __global__ __launch_bounds__(kJoinThreads) void join_bytes_kernel(
     uint32_t *__restrict__ b_count, unsigned long long *__restrict__ sums) {
     __shared__ uint8_t s_lut4[256];
     __shared__ unsigned long long s_sums[4];
-    s_lut4[threadIdx.x] = lookup_code4(threadIdx.x);
+    s_lut4[threadIdx.x] = code4(threadIdx.x);
     if (threadIdx.x < 4) s_sums[threadIdx.x] = 0;
     __syncthreads();
     JoinSums t;
@@ -87,20 +74,9 @@ __global__ __launch_bounds__(kJoinThreads) void join_bytes_kernel(
          u += (uint64_t)gridDim.x * kJoinThreads) {
         const uint8_t *pa = sba_a + starts_a[heads_a[u]];
         const bool rc_a = CANON && canon_is_rc<4>(pa, k, s_lut4);
-        uint64_t lo = 0, hi = n_b;
-        while (lo < hi) {  // B's k-mers below A's
-            const uint64_t mid = (lo + hi) >> 1;
-            if (join_cmp<CANON>(sba_b + starts_b[mid], pa, rc_a, k, s_lut4) < 0) lo = mid + 1;
-            else hi = mid;
-        }
-        const uint64_t lb = lo;
-        hi = n_b;
-        while (lo < hi) {  // ... and not above it, from the lower bound on
-            const uint64_t mid = (lo + hi) >> 1;
-            if (join_cmp<CANON>(sba_b + starts_b[mid], pa, rc_a, k, s_lut4) <= 0) lo = mid + 1;
-            else hi = mid;
-        }
-        const uint32_t cnt = (uint32_t)(lo - lb);
+        uint64_t lb;
+        uint32_t cnt;
+        bytes_range<CANON>(sba_b, starts_b, n_b, k, s_lut4, SoughtStrand{pa, s_lut4, k, rc_a}, &lb, &cnt);
         b_first[u] = (uint32_t)lb;  // (n_b <= 2^32 - 1: GK_E_LIMIT)
         b_count[u] = cnt;
         if (cnt) t.add(count_a[u], cnt);
@@ -277,14 +253,12 @@ extern "C" int gk_join(gk_ctx *a, gk_ctx *b, uint32_t flags, gk_join_stats *stat
     // path: the merge of the keys when both sides hold final 2-bit keys of one layout, else the bytes
     const bool keys_ok = lookup_keys_usable(a) && lookup_keys_usable(b) && a->spec.symbols == b->spec.symbols;
     bool use_keys = keys_ok;
-    if (const char *p = opt("GKM_JOIN_PATH")) {
-        if (std::strcmp(p, "bytes") == 0) use_keys = false;
-        else if (std::strcmp(p, "keys") == 0) {
-            if (!keys_ok)
-                return fail(a, GK_E_UNSUPPORTED,
-                            "GKM_JOIN_PATH=keys: the contexts do not both hold final one-word 2-bit forward keys");
-        } else return fail(a, GK_E_ARG, "GKM_JOIN_PATH must be 'bytes' or 'keys'");
-    }
+    const int path = query::parse_path(opt("GKM_JOIN_PATH"));
+    if (path < 0) return fail(a, GK_E_ARG, "GKM_JOIN_PATH must be 'bytes' or 'keys'");
+    if (path == query::kPathKeys && !keys_ok)
+        return fail(a, GK_E_UNSUPPORTED,
+                    "GKM_JOIN_PATH=keys: the contexts do not both hold final one-word 2-bit forward keys");
+    if (path == query::kPathBytes) use_keys = false;
 
     uint32_t *d_first, *d_count;
     unsigned long long *d_sums;

@@ -6,7 +6,8 @@
 // Two paths, the same answers ("Lookup"):
 //   bytes  one thread per query: lower and upper bound over the sorted starts, comparing the sba bytes
 //          at starts[mid] with the query in 4-bit symbol codes ('$' / end = 0, below every letter);
-//          canonical orders compare the k-mer's canonical form (gkm_canon.h).  Always valid.
+//          canonical orders compare the k-mer's canonical form.  Always valid.  The search and the
+//          comparison are gkm_bytes_search.h's, shared with gk_join and gk_screen.
 //   keys   final one-word 2-bit keys in sorted order and A/C/G/T-only queries: the query becomes its
 //          2 q-bit prefix and the search runs over keys[cur] >> shift, inside the bucket a prefix
 //          directory of the top D key bits gives (built by the first such lookup after a sort).
@@ -16,7 +17,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "gkm_canon.h"
+#include "gkm_bytes_search.h"
 #include "gkm_internal.h"
 #include "gkm_lookup_host.h"
 #include "gkm_lookup_search.h"
@@ -31,22 +32,9 @@ constexpr int kLookupDirBits = 22;          // 4 Mi buckets, 16 MiB of uint32
 // ---------------------------------------------------------------------------------------------
 // byte path
 // ---------------------------------------------------------------------------------------------
-// sign of (k-mer at p, canonical form if CANON) - (query), over q symbols in 4-bit codes.  The
-// query's codes: s_q[t * 256] (this thread's column of the block's LDS copy) when LDS, else lut4 of
-// the query bytes qg[t].  A '$' (code 0) in the k-mer is below every query code and ends the loop,
-// so no byte after the '$' that ends the contig (or the pad after the sba) is read.
-template <bool CANON, bool LDS>
-__device__ __forceinline__ int query_cmp(const uint8_t *__restrict__ p, const uint8_t *s_q,
-                                         const uint8_t *__restrict__ qg, int q, const uint8_t *lut4) {
-    const bool rc = CANON && canon_is_rc<4>(p, q, lut4);
-    for (int t = 0; t < q; ++t) {
-        const uint32_t x = CANON ? canon_sym<4>(p, q, t, rc, lut4) : (uint32_t)lut4[p[t]];
-        const uint32_t y = LDS ? (uint32_t)s_q[t * kLookupThreads] : (uint32_t)lut4[qg[t]];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return 0;
-}
-
+// bytes_range (gkm_bytes_search.h); the query's codes: this thread's column of the block's LDS copy
+// when LDS (SoughtLds strides it by 256), else lut4 of the query bytes where they lie
+static_assert(kLookupThreads == 256);
 template <bool CANON, bool LDS>
 __global__ __launch_bounds__(kLookupThreads) void lookup_bytes_kernel(
     const uint8_t *__restrict__ sba, const uint32_t *__restrict__ starts, uint64_t n,
@@ -54,29 +42,16 @@ __global__ __launch_bounds__(kLookupThreads) void lookup_bytes_kernel(
     uint32_t *__restrict__ count) {
     extern __shared__ uint8_t s_query[];  // LDS: [qlen][256] symbol codes, one column per thread
     __shared__ uint8_t s_lut4[256];
-    s_lut4[threadIdx.x] = lookup_code4(threadIdx.x);
+    s_lut4[threadIdx.x] = code4(threadIdx.x);
     __syncthreads();
-    const uint8_t *s_q = s_query + threadIdx.x;
     for (uint64_t i = blockIdx.x * (uint64_t)kLookupThreads + threadIdx.x; i < m;
          i += (uint64_t)gridDim.x * kLookupThreads) {
         const uint8_t *qg = queries + i * qlen;
+        const int q = (int)qlen;
         if (LDS)  // (a thread reads back only the column it wrote: no barrier)
             for (uint32_t t = 0; t < qlen; ++t) s_query[t * kLookupThreads + threadIdx.x] = s_lut4[qg[t]];
-        uint64_t lo = 0, hi = n;
-        while (lo < hi) {  // k-mers below the query
-            const uint64_t mid = (lo + hi) >> 1;
-            if (query_cmp<CANON, LDS>(sba + starts[mid], s_q, qg, (int)qlen, s_lut4) < 0) lo = mid + 1;
-            else hi = mid;
-        }
-        const uint64_t lb = lo;
-        hi = n;
-        while (lo < hi) {  // ... and not above it, from the lower bound on
-            const uint64_t mid = (lo + hi) >> 1;
-            if (query_cmp<CANON, LDS>(sba + starts[mid], s_q, qg, (int)qlen, s_lut4) <= 0) lo = mid + 1;
-            else hi = mid;
-        }
-        first[i] = lb;
-        count[i] = (uint32_t)(lo - lb);
+        if (LDS) bytes_range<CANON>(sba, starts, n, q, s_lut4, SoughtLds{s_query + threadIdx.x}, &first[i], &count[i]);
+        else bytes_range<CANON>(sba, starts, n, q, s_lut4, SoughtBytes{qg, s_lut4}, &first[i], &count[i]);
     }
 }
 
@@ -147,6 +122,31 @@ int lookup_build_dir(gk_ctx *c, uint32_t **out) {
     return GK_OK;
 }
 
+// Pinned staging (grow-only, kept for the context's life): a copy from or to pageable memory is
+// staged by the runtime at a fraction of the link's rate and holds the host meanwhile; with two
+// pinned slots the host fills slot s while the copy engine and the kernel work on slot s ^ 1.
+int stage_reserve(gk_ctx *c, uint64_t slot_bytes) {
+    if (c->stage_pin_cap < 2 * slot_bytes) {
+        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->stage_pin) (void)hipHostFree(c->stage_pin);
+        c->stage_pin = nullptr;
+        c->stage_pin_cap = 0;
+        GK_TRY_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&c->stage_pin), 2 * slot_bytes, hipHostMallocDefault));
+        c->stage_pin_cap = 2 * slot_bytes;
+    }
+    for (hipEvent_t &ev : c->stage_ev)
+        if (!ev) GK_TRY_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return GK_OK;
+}
+
+int fail_alphabet(gk_ctx *c, const uint8_t *queries, uint64_t bad, uint32_t qlen) {
+    const uint8_t b = queries[bad];
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "query %llu holds byte 0x%02x ('%c') outside the alphabet ABCDGHKMNRSTVWY",
+                  (unsigned long long)(bad / qlen), (unsigned)b, (b >= 32 && b < 127) ? (char)b : '?');
+    return fail(c, GK_E_ALPHABET, msg);
+}
+
 }  // namespace gkm
 
 using namespace gkm;
@@ -169,25 +169,17 @@ extern "C" int gk_lookup(gk_ctx *c, const uint8_t *queries, uint64_t m, uint32_t
     if (m > UINT64_MAX / qlen) return fail(c, GK_E_ARG, "query batch too large");
     bool all_acgt = false;
     const int64_t bad = lookup::validate_queries(queries, m, qlen, &all_acgt);
-    if (bad >= 0) {
-        const uint8_t b = queries[bad];
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "query %llu holds byte 0x%02x ('%c') outside the alphabet ABCDGHKMNRSTVWY",
-                      (unsigned long long)((uint64_t)bad / qlen), (unsigned)b, (b >= 32 && b < 127) ? (char)b : '?');
-        return fail(c, GK_E_ALPHABET, msg);
-    }
+    if (bad >= 0) return fail_alphabet(c, queries, (uint64_t)bad, qlen);
     // path: the keys when the context holds final 2-bit keys and the queries are ACGT, else the bytes
     const bool keys_ok = lookup_keys_usable(c);
     bool use_keys = keys_ok && all_acgt;
-    if (const char *p = opt("GKM_LOOKUP_PATH")) {
-        if (std::strcmp(p, "bytes") == 0) use_keys = false;
-        else if (std::strcmp(p, "keys") == 0) {
-            if (!use_keys)
-                return fail(c, GK_E_UNSUPPORTED,
-                            keys_ok ? "GKM_LOOKUP_PATH=keys: a query holds a letter other than A, C, G, T"
-                                    : "GKM_LOOKUP_PATH=keys: the context holds no final one-word 2-bit forward keys");
-        } else return fail(c, GK_E_ARG, "GKM_LOOKUP_PATH must be 'bytes' or 'keys'");
-    }
+    const int path = query::parse_path(opt("GKM_LOOKUP_PATH"));
+    if (path < 0) return fail(c, GK_E_ARG, "GKM_LOOKUP_PATH must be 'bytes' or 'keys'");
+    if (path == query::kPathKeys && !use_keys)
+        return fail(c, GK_E_UNSUPPORTED,
+                    keys_ok ? "GKM_LOOKUP_PATH=keys: a query holds a letter other than A, C, G, T"
+                            : "GKM_LOOKUP_PATH=keys: the context holds no final one-word 2-bit forward keys");
+    if (path == query::kPathBytes) use_keys = false;
     const char *dir_opt = opt("GKM_LOOKUP_DIR");
     const bool use_dir = !(dir_opt && std::strcmp(dir_opt, "0") == 0);
     const uint64_t chunk = lookup::chunk_size(opt("GKM_LOOKUP_CHUNK"), qlen);
@@ -205,28 +197,18 @@ extern "C" int gk_lookup(gk_ctx *c, const uint8_t *queries, uint64_t m, uint32_t
     GK_TRY_HIP(c, scratch(c, "lookup_q", cap * qlen, &d_q));
     GK_TRY_HIP(c, scratch(c, "lookup_first", cap, &d_first));
     GK_TRY_HIP(c, scratch(c, "lookup_count", cap, &d_count));
-    // Pinned staging, two slots (grow-only, kept for the context's life; chunk_size bounds a slot at
-    // kChunk queries and kChunkBytes of query bytes, so the block is at most ~150 MiB): a copy from or to pageable memory is staged by the runtime at a
-    // fraction of the link's rate and holds the host meanwhile; here the host fills slot s (a memcpy,
-    // or the canonical form of each query) while the copy engine and the kernel work on slot s ^ 1,
-    // and a chunk's results leave their slot for the caller's arrays two chunks later.
+    // The pinned staging's two slots (stage_reserve; chunk_size bounds a slot at kChunk queries and
+    // kChunkBytes of query bytes, so the block is at most ~150 MiB): the host fills slot s (a memcpy, or
+    // the canonical form of each query) while the copy engine and the kernel work on slot s ^ 1, and a
+    // chunk's results leave their slot for the caller's arrays two chunks later.
     const uint64_t q_bytes = (cap * qlen + 255) / 256 * 256, f_bytes = (8 * cap + 255) / 256 * 256;
     const uint64_t slot_bytes = q_bytes + f_bytes + (4 * cap + 255) / 256 * 256;
-    if (c->lookup_pin_cap < 2 * slot_bytes) {
-        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->lookup_pin) (void)hipHostFree(c->lookup_pin);
-        c->lookup_pin = nullptr;
-        c->lookup_pin_cap = 0;
-        GK_TRY_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&c->lookup_pin), 2 * slot_bytes, hipHostMallocDefault));
-        c->lookup_pin_cap = 2 * slot_bytes;
-    }
-    for (hipEvent_t &ev : c->lookup_ev)
-        if (!ev) GK_TRY_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    // a chunk's results, from its slot to the caller's arrays (after lookup_ev[slot] or a stream sync)
+    if (int rc = stage_reserve(c, slot_bytes)) return rc;
+    // a chunk's results, from its slot to the caller's arrays (after stage_ev[slot] or a stream sync)
     auto drain = [&](uint64_t ci) {
         uint64_t off, len;
         lookup::chunk_range(m, chunk, ci, &off, &len);
-        const uint8_t *slot = c->lookup_pin + (ci & 1) * slot_bytes;
+        const uint8_t *slot = c->stage_pin + (ci & 1) * slot_bytes;
         std::memcpy(first + off, slot + q_bytes, 8 * len);
         std::memcpy(count + off, slot + q_bytes + f_bytes, 4 * len);
     };
@@ -237,9 +219,9 @@ extern "C" int gk_lookup(gk_ctx *c, const uint8_t *queries, uint64_t m, uint32_t
     for (uint64_t ci = 0; ci < nchunks; ++ci) {
         uint64_t off, len;
         lookup::chunk_range(m, chunk, ci, &off, &len);
-        uint8_t *slot = c->lookup_pin + (ci & 1) * slot_bytes;
+        uint8_t *slot = c->stage_pin + (ci & 1) * slot_bytes;
         if (ci >= 2) {  // the slot's previous chunk: wait for its results and hand them over
-            GK_TRY_HIP(c, hipEventSynchronize(c->lookup_ev[ci & 1]));
+            GK_TRY_HIP(c, hipEventSynchronize(c->stage_ev[ci & 1]));
             drain(ci - 2);
         }
         const uint8_t *src = queries + off * qlen;
@@ -275,7 +257,7 @@ extern "C" int gk_lookup(gk_ctx *c, const uint8_t *queries, uint64_t m, uint32_t
         timer_end(c, tslot);
         GK_TRY_HIP(c, hipMemcpyAsync(slot + q_bytes, d_first, 8 * len, hipMemcpyDeviceToHost, c->stream));
         GK_TRY_HIP(c, hipMemcpyAsync(slot + q_bytes + f_bytes, d_count, 4 * len, hipMemcpyDeviceToHost, c->stream));
-        GK_TRY_HIP(c, hipEventRecord(c->lookup_ev[ci & 1], c->stream));
+        GK_TRY_HIP(c, hipEventRecord(c->stage_ev[ci & 1], c->stream));
     }
     GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
     if (nchunks >= 2) drain(nchunks - 2);

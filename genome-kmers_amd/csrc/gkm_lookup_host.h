@@ -5,8 +5,9 @@
 
 #include <stdint.h>
 
-#include <cstdlib>
 #include <cstring>
+
+#include "gkm_query_host.h"
 
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -115,18 +116,11 @@ inline void canonical_query(const uint8_t *q, uint32_t qlen, uint8_t *dst) {
 }
 
 // queries per launch: kChunk, cut so that a chunk's query bytes stay within kChunkBytes for long
-// queries.  The knob (tests: several launches from a small batch) can only lower it, never raise
-// it, so the device scratch and the pinned staging stay bounded whatever its value; nullptr / empty
-// / 0 / not a number: the default
+// queries; the knob only lowers it (query::knob_below)
 constexpr uint64_t kChunkBytes = 64ull << 20;
 inline uint64_t chunk_size(const char *value, uint32_t qlen) {
     const uint64_t fit = kChunkBytes / qlen ? kChunkBytes / qlen : 1;
-    const uint64_t def = kChunk < fit ? kChunk : fit;
-    if (!value || !*value) return def;
-    char *end = nullptr;
-    const unsigned long long v = std::strtoull(value, &end, 10);
-    if (end == value || *end != 0 || v == 0) return def;
-    return (uint64_t)v < def ? (uint64_t)v : def;
+    return query::knob_below(value, kChunk < fit ? kChunk : fit);
 }
 
 inline uint64_t chunk_count(uint64_t m, uint64_t chunk) { return m / chunk + (m % chunk != 0); }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kMismatchThreads) void mismatch_kernel(
     uint64_t rec_cap, unsigned long long *__restrict__ rec_n) {
     __shared__ uint8_t s_lut4[256];
     if (W == 2) {
-        s_lut4[threadIdx.x] = lookup_code4(threadIdx.x);
+        s_lut4[threadIdx.x] = code4(threadIdx.x);
         __syncthreads();
     }
     // W = 2: the nibbles of the first qlen symbols in each word (no shift by 64 at 16 symbols)
@@ -197,27 +197,19 @@ extern "C" int gk_lookup_mismatch(gk_ctx *c, const uint8_t *queries, uint64_t m,
     if (m > (1ull << 32)) return fail(c, GK_E_ARG, "query batch too large");
     bool all_acgt = false;
     const int64_t bad = lookup::validate_queries(queries, m, qlen, &all_acgt);
-    if (bad >= 0) {
-        const uint8_t b = queries[bad];
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "query %llu holds byte 0x%02x ('%c') outside the alphabet ABCDGHKMNRSTVWY",
-                      (unsigned long long)((uint64_t)bad / qlen), (unsigned)b, (b >= 32 && b < 127) ? (char)b : '?');
-        return fail(c, GK_E_ALPHABET, msg);
-    }
+    if (bad >= 0) return fail_alphabet(c, queries, (uint64_t)bad, qlen);
     // path: the keys when the context holds final 2-bit keys that cover qlen and the queries (and so
     // their complements) are ACGT, else the bytes
     const bool keys_ok = lookup_keys_usable(c) && qlen <= (uint32_t)c->spec.symbols;
     bool use_keys = keys_ok && all_acgt;
-    if (const char *p = opt("GKM_MISMATCH_PATH")) {
-        if (std::strcmp(p, "bytes") == 0) use_keys = false;
-        else if (std::strcmp(p, "keys") == 0) {
-            if (!use_keys)
-                return fail(c, GK_E_UNSUPPORTED,
-                            keys_ok ? "GKM_MISMATCH_PATH=keys: a query holds a letter other than A, C, G, T"
-                                    : "GKM_MISMATCH_PATH=keys: the context holds no final one-word 2-bit forward "
-                                      "keys of at least the query length");
-        } else return fail(c, GK_E_ARG, "GKM_MISMATCH_PATH must be 'bytes' or 'keys'");
-    }
+    const int path = query::parse_path(opt("GKM_MISMATCH_PATH"));
+    if (path < 0) return fail(c, GK_E_ARG, "GKM_MISMATCH_PATH must be 'bytes' or 'keys'");
+    if (path == query::kPathKeys && !use_keys)
+        return fail(c, GK_E_UNSUPPORTED,
+                    keys_ok ? "GKM_MISMATCH_PATH=keys: a query holds a letter other than A, C, G, T"
+                            : "GKM_MISMATCH_PATH=keys: the context holds no final one-word 2-bit forward "
+                              "keys of at least the query length");
+    if (path == query::kPathBytes) use_keys = false;
     const uint32_t nd = max_mismatches + 1;
     if (c->n == 0) {
         std::memset(counts, 0, 8 * m * nd);

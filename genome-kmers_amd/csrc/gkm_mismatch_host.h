@@ -7,8 +7,8 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
 
+#include "gkm_canon.h"
 #include "gkm_lookup_host.h"
 
 namespace gkm {
@@ -21,14 +21,7 @@ constexpr uint32_t kMaxQlen = 32;  // one 64-bit word of 2-bit codes, two of 4-b
 // under 20 MiB; GKM_MISMATCH_CHUNK can lower it (chunk_size)
 constexpr uint64_t kChunk = 1ull << 16;
 
-// nullptr / empty / 0 / not a number: the default; the knob only lowers it
-inline uint64_t chunk_size(const char *value) {
-    if (!value || !*value) return kChunk;
-    char *end = nullptr;
-    const unsigned long long v = std::strtoull(value, &end, 10);
-    if (end == value || *end != 0 || v == 0) return kChunk;
-    return (uint64_t)v < kChunk ? (uint64_t)v : kChunk;
-}
+inline uint64_t chunk_size(const char *value) { return query::knob_below(value, kChunk); }
 using lookup::chunk_count;
 using lookup::chunk_range;
 
@@ -39,13 +32,8 @@ inline void reverse_complement(const uint8_t *q, uint32_t qlen, uint8_t *dst) {
 
 // A C G T -> 0 1 2 3 (gkm_canon.h canon_code<2>)
 inline uint32_t code2(uint8_t b) { return ((b >> 1) ^ (b >> 2)) & 3u; }
-// '$' and anything else 0, A B C D G H K M N R S T V W Y -> 1..15 (gkm_lookup.hip lookup_code4)
-inline uint32_t code4(uint8_t b) {
-    constexpr char kOrder[] = "ABCDGHKMNRSTVWY";
-    for (uint32_t i = 0; i < 15; ++i)
-        if (b == (uint8_t)kOrder[i]) return i + 1;
-    return 0;
-}
+// '$' and anything else 0, A B C D G H K M N R S T V W Y -> 1..15: the kernels' own
+using gkm::code4;
 
 // the 2 qlen-bit prefix word of an A/C/G/T query, first base most significant, right-aligned (as
 // lookup_keys_kernel builds it): qlen <= 32, no shift by 64 and no mask at qlen = 32

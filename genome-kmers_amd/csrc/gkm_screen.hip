@@ -11,7 +11,9 @@
 //          advance in lockstep.  A window with a letter other than A, C, G, T counts 0 unsearched: the
 //          index is A/C/G/T-only.
 //   bytes  one search per window over the sorted starts, comparing sba bytes with the read's in 4-bit
-//          codes; canonical orders compare canonical forms on both sides.  Always valid.
+//          codes; canonical orders compare canonical forms on both sides.  Always valid.  The search
+//          and the comparison are gkm_bytes_search.h's (gk_lookup's and gk_join's), the window read
+//          in place; a byte outside the alphabet in it is code 0 and fails the call.
 // A tile finds the sequences of its first and last position by a search over `offsets` that the 64
 // lanes of one wave share, keeps the boundaries between them in LDS (kScreenBounds at a time: a tile
 // with more -- many empty or very short reads -- takes them in several passes), sums per sequence in
@@ -20,7 +22,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "gkm_canon.h"
+#include "gkm_bytes_search.h"
 #include "gkm_internal.h"
 #include "gkm_lookup_search.h"
 #include "gkm_screen_host.h"
@@ -87,41 +89,6 @@ __device__ __forceinline__ int rc_sign(const uint8_t *__restrict__ q, int K, con
     return 0;
 }
 
-// sign of (k-mer at p, canonical form if CANON) - (the window q, its reverse complement if qrc) over K
-// symbols in 4-bit codes: lookup_bytes_kernel's comparison with the query read in place.  A '$' in
-// the k-mer is below every letter and ends the loop, so no byte after a contig's end is read.
-template <bool CANON>
-__device__ __forceinline__ int screen_cmp(const uint8_t *__restrict__ p, const uint8_t *__restrict__ q, int K,
-                                          bool qrc, const uint8_t *lut4) {
-    const bool rc = CANON && canon_is_rc<4>(p, K, lut4);
-    for (int t = 0; t < K; ++t) {
-        const uint32_t x = CANON ? canon_sym<4>(p, K, t, rc, lut4) : (uint32_t)lut4[p[t]];
-        const uint32_t y = qrc ? comp_sym<4>(lut4[q[K - 1 - t]]) : (uint32_t)lut4[q[t]];
-        if (x != y) return x < y ? -1 : 1;
-        if (x == 0) return 0;  // (a byte outside the alphabet in q: the call fails; stop at the '$')
-    }
-    return 0;
-}
-
-template <bool CANON>
-__device__ __forceinline__ uint32_t byte_count(const ScreenArgs &a, const uint8_t *__restrict__ q, int K, bool qrc,
-                                               const uint8_t *lut4) {
-    uint64_t lo = 0, hi = a.n;
-    while (lo < hi) {  // k-mers below the window
-        const uint64_t mid = (lo + hi) >> 1;
-        if (screen_cmp<CANON>(a.sba + a.starts[mid], q, K, qrc, lut4) < 0) lo = mid + 1;
-        else hi = mid;
-    }
-    const uint64_t lb = lo;
-    hi = a.n;
-    while (lo < hi) {  // ... and not above it, from the lower bound on
-        const uint64_t mid = (lo + hi) >> 1;
-        if (screen_cmp<CANON>(a.sba + a.starts[mid], q, K, qrc, lut4) <= 0) lo = mid + 1;
-        else hi = mid;
-    }
-    return (uint32_t)(lo - lb);
-}
-
 // MODE 0: keys, 1: bytes, 2: bytes of a canonical order.  One block per tile of kScreenTile positions.
 template <int MODE>
 __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs a) {
@@ -135,7 +102,7 @@ __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs
     __shared__ uint64_t s_j[2];
     const int tid = threadIdx.x;
     const int K = (int)a.K;
-    s_lut4[tid] = lookup_code4(tid);
+    s_lut4[tid] = code4(tid);
     const uint64_t t0 = blockIdx.x * (uint64_t)kScreenTile;  // in the chunk
     const uint64_t t1 = t0 + kScreenTile < a.nslots ? t0 + kScreenTile : a.nslots;
     const uint64_t g0 = a.base + t0, g1 = a.base + t1;       // in the batch
@@ -264,8 +231,16 @@ __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs
                     if (p + K <= s_tab[jr]) {
                         const uint8_t *q = a.bytes + (p - a.base);
                         const int s = (MODE == 2 || a.both) ? rc_sign(q, K, s_lut4) : 0;
-                        cw = byte_count<MODE == 2>(a, q, K, MODE == 2 && s < 0, s_lut4);
-                        if (MODE == 1 && a.both && s != 0) cw += byte_count<false>(a, q, K, true, s_lut4);
+                        // the window's count (gkm_bytes_search.h), the window read in place: its
+                        // canonical form on a canonical order, its other strand too if a.both
+                        uint64_t f;
+                        bytes_range<MODE == 2>(a.sba, a.starts, a.n, K, s_lut4,
+                                               SoughtStrand{q, s_lut4, K, MODE == 2 && s < 0}, &f, &cw);
+                        if (MODE == 1 && a.both && s != 0) {
+                            uint32_t cr;
+                            bytes_range<false>(a.sba, a.starts, a.n, K, s_lut4, SoughtStrand{q, s_lut4, K, true}, &f, &cr);
+                            cw += cr;
+                        }
                     }
                     if (a.wc) a.wc[p - a.base] = cw;
                     if (jr != cur) {
@@ -328,16 +303,11 @@ extern "C" int gk_screen(gk_ctx *c, const uint8_t *seqs, const uint64_t *offsets
     // other letter counts 0 there), else the bytes
     const bool keys_ok = lookup_keys_usable(c);
     bool use_keys = keys_ok;
-    switch (screen::parse_path(opt("GKM_SCREEN_PATH"))) {
-        case 0: break;
-        case 1: use_keys = false; break;
-        case 2:
-            if (!keys_ok)
-                return fail(c, GK_E_UNSUPPORTED,
-                            "GKM_SCREEN_PATH=keys: the context holds no final one-word 2-bit forward keys");
-            break;
-        default: return fail(c, GK_E_ARG, "GKM_SCREEN_PATH must be 'bytes' or 'keys'");
-    }
+    const int path = query::parse_path(opt("GKM_SCREEN_PATH"));
+    if (path < 0) return fail(c, GK_E_ARG, "GKM_SCREEN_PATH must be 'bytes' or 'keys'");
+    if (path == query::kPathKeys && !keys_ok)
+        return fail(c, GK_E_UNSUPPORTED, "GKM_SCREEN_PATH=keys: the context holds no final one-word 2-bit forward keys");
+    if (path == query::kPathBytes) use_keys = false;
     const uint64_t chunk = screen::chunk_bytes(opt("GKM_SCREEN_CHUNK"), K);
     const uint64_t step = screen::chunk_step(chunk, K);
 
@@ -358,22 +328,13 @@ extern "C" int gk_screen(gk_ctx *c, const uint8_t *seqs, const uint64_t *offsets
     GK_TRY_HIP(c, scratch(c, "screen_occ", nseq, &d_occ));
     GK_TRY_HIP(c, scratch(c, "screen_bad", 1, &d_bad));
     if (window_count) GK_TRY_HIP(c, scratch(c, "screen_wc", cap_slots, &d_wc));
-    // gk_lookup's pinned staging, two slots (grow-only; both calls leave it idle when they return): the
-    // host fills slot s while the copy engine and the kernel work on slot s ^ 1, and a chunk's window
-    // counts leave their slot for the caller's array two chunks later
+    // the pinned staging's two slots (stage_reserve): the host fills slot s while the copy engine and
+    // the kernel work on slot s ^ 1, and a chunk's window counts leave their slot for the caller's
+    // array two chunks later
     const uint64_t b_bytes = (cap_bytes + 255) / 256 * 256;
     const uint64_t w_bytes = window_count ? (4 * cap_slots + 255) / 256 * 256 : 0;
     const uint64_t slot_bytes = b_bytes + w_bytes + 256;  // (the last 256: the chunk's copy of d_bad)
-    if (c->lookup_pin_cap < 2 * slot_bytes) {
-        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->lookup_pin) (void)hipHostFree(c->lookup_pin);
-        c->lookup_pin = nullptr;
-        c->lookup_pin_cap = 0;
-        GK_TRY_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&c->lookup_pin), 2 * slot_bytes, hipHostMallocDefault));
-        c->lookup_pin_cap = 2 * slot_bytes;
-    }
-    for (hipEvent_t &ev : c->lookup_ev)
-        if (!ev) GK_TRY_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (int rc = stage_reserve(c, slot_bytes)) return rc;
 
     GK_TRY_HIP(c, hipMemcpyAsync(d_off, offsets, 8 * (nseq + 1), hipMemcpyHostToDevice, c->stream));
     GK_TRY_HIP(c, hipMemsetAsync(d_present, 0, 4 * nseq, c->stream));
@@ -397,19 +358,19 @@ extern "C" int gk_screen(gk_ctx *c, const uint8_t *seqs, const uint64_t *offsets
     a.wc = d_wc;
     a.bad = d_bad;
     const uint64_t nchunks = screen::chunk_count(total, chunk, K);
-    auto drain = [&](uint64_t ci) {  // (after lookup_ev[slot] or a stream sync)
+    auto drain = [&](uint64_t ci) {  // (after stage_ev[slot] or a stream sync)
         if (!window_count) return;
         uint64_t start, nslots, nbytes;
         screen::chunk_range(total, chunk, K, ci, &start, &nslots, &nbytes);
-        std::memcpy(window_count + start, c->lookup_pin + (ci & 1) * slot_bytes + b_bytes, 4 * nslots);
+        std::memcpy(window_count + start, c->stage_pin + (ci & 1) * slot_bytes + b_bytes, 4 * nslots);
     };
     const char *timer_name = use_keys ? "screen_keys" : "screen_bytes";
     for (uint64_t ci = 0; ci < nchunks; ++ci) {
         uint64_t start, nslots, nbytes;
         screen::chunk_range(total, chunk, K, ci, &start, &nslots, &nbytes);
-        uint8_t *slot = c->lookup_pin + (ci & 1) * slot_bytes;
+        uint8_t *slot = c->stage_pin + (ci & 1) * slot_bytes;
         if (ci >= 2) {  // the slot's previous chunk: wait for it and hand its counts over
-            GK_TRY_HIP(c, hipEventSynchronize(c->lookup_ev[ci & 1]));
+            GK_TRY_HIP(c, hipEventSynchronize(c->stage_ev[ci & 1]));
             unsigned long long seen;  // a byte outside the alphabet so far: launch nothing more
             std::memcpy(&seen, slot + b_bytes + w_bytes, 8);
             if (seen != ~0ull) break;
@@ -432,7 +393,7 @@ extern "C" int gk_screen(gk_ctx *c, const uint8_t *seqs, const uint64_t *offsets
         if (window_count)
             GK_TRY_HIP(c, hipMemcpyAsync(slot + b_bytes, d_wc, 4 * nslots, hipMemcpyDeviceToHost, c->stream));
         GK_TRY_HIP(c, hipMemcpyAsync(slot + b_bytes + w_bytes, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
-        GK_TRY_HIP(c, hipEventRecord(c->lookup_ev[ci & 1], c->stream));
+        GK_TRY_HIP(c, hipEventRecord(c->stage_ev[ci & 1], c->stream));
     }
     // the smallest bad position of the chunks launched: the chunks run in order, so it is the batch's
     unsigned long long bad = 0;

@@ -6,8 +6,7 @@
 
 #include <stdint.h>
 
-#include <cstdlib>
-#include <cstring>
+#include "gkm_query_host.h"
 
 namespace gkm {
 namespace screen {
@@ -32,23 +31,12 @@ inline OffsetError validate_offsets(const uint64_t *offsets, uint64_t nseq, uint
     return kOffsetsOk;
 }
 
-// GKM_SCREEN_PATH: 0 unset (the call chooses), 1 bytes, 2 keys, -1 any other value
-inline int parse_path(const char *value) {
-    if (!value) return 0;
-    if (std::strcmp(value, "bytes") == 0) return 1;
-    if (std::strcmp(value, "keys") == 0) return 2;
-    return -1;
-}
+using query::parse_path;  // GKM_SCREEN_PATH
 
-// bytes per launch for windows of K bytes: kChunkBytes, lowered by the knob (never raised; nullptr /
-// empty / 0 / not a number: the default), and at least K so that a chunk holds one whole window
+// bytes per launch for windows of K bytes: kChunkBytes, lowered by the knob (query::knob_below), and
+// at least K so that a chunk holds one whole window
 inline uint64_t chunk_bytes(const char *value, uint32_t K) {
-    uint64_t c = kChunkBytes;
-    if (value && *value) {
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(value, &end, 10);
-        if (end != value && *end == 0 && v != 0 && (uint64_t)v < c) c = (uint64_t)v;
-    }
+    const uint64_t c = query::knob_below(value, kChunkBytes);
     return c < K ? (uint64_t)K : c;
 }
 
