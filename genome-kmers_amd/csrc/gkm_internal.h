@@ -53,6 +53,27 @@ struct KeySpec {
     int acgt_only;    // MSD of a mixed sba's ACGT-only k-mers (2-bit keys; the rest sorted apart, gkm_split.hip)
     int digits() const { return (total_bits + kRadixBits - 1) / kRadixBits; }
 };
+// forward keys of `symbols` symbols of `bits` bits and a length field of lenbits bits: total_bits and
+// words follow (a key too wide for kMaxWords shows in words; its total_bits is not used)
+inline KeySpec key_spec(int bits, uint64_t symbols, int lenbits, int min_len) {
+    KeySpec ks{};
+    ks.bits = bits;
+    ks.symbols = (int)symbols;
+    ks.lenbits = lenbits;
+    ks.min_len = min_len;
+    const uint64_t tb = (uint64_t)bits * symbols + (uint64_t)lenbits;
+    ks.total_bits = (int)tb;
+    ks.words = (int)((tb + 63) / 64);
+    return ks;
+}
+inline int bit_width(uint64_t v) {
+    int b = 0;
+    while (v) {
+        ++b;
+        v >>= 1;
+    }
+    return b;
+}
 
 struct Timer {
     std::string name;
@@ -156,13 +177,14 @@ struct gk_ctx {
     bool unique_valid = false;
 
     // gk_join's result for this context as side A (gkm_join.hip; scratch "join_first" / "join_count":
-    // uint32[join_n], aligned with the unique view): valid while join_valid && unique_valid, so it is
-    // dropped wherever unique_valid is; gk_unique_counts clears join_valid when it rebuilds a dropped view
+    // uint32[join_n], aligned with the unique view): valid while join_valid && unique_valid, so it goes
+    // with the unique view (drop_order_views); gk_unique_counts clears join_valid when it rebuilds a dropped view
     bool join_valid = false;
     uint64_t join_n = 0;
 
     // gk_lookup's prefix directory over keys[cur] (gkm_lookup.hip; scratch "lookup_dir"): built by the
-    // first key-path lookup after a sort, dropped wherever sorted / keys_valid / heads_valid are reset
+    // first key-path lookup after a sort, dropped with the order's views (drop_order_views) and with the
+    // key buffers (ensure_elems)
     bool lookup_dir_valid = false;
     int lookup_dir_bits = 0;   // D: the directory indexes the top D key bits
     // pinned host staging that gk_lookup and gk_screen share (stage_reserve; both leave it idle when
@@ -211,6 +233,48 @@ struct gk_ctx {
 };
 
 // ---------------------------------------------------------------------------------------------
+// the k-mer state: the one place that writes the flags under "k-mers" and the cached views' valid bits
+// together (a view's own file sets its bit when it builds the view; ensure_elems drops the keys it frees)
+// ---------------------------------------------------------------------------------------------
+namespace gkm {
+
+// The order of the k-mers changes: every view cached on it goes -- the group heads, the unique view
+// (and with it gk_join's result, which is valid only while unique_valid is), gk_lookup's directory,
+// and the claim that vals is gk_sort's order of the whole enumeration.  A view added later is
+// dropped here.
+inline void drop_order_views(gk_ctx *c) {
+    c->heads_valid = c->unique_valid = c->lookup_dir_valid = c->enum_sorted = false;
+}
+
+// "The k-mer set is now this": no k-mers, the enumeration (its starts written on demand,
+// materialize_starts), or starts that vals[cur] holds.  Nothing derived from the earlier set or its
+// order survives: not the sort, not the keys, none of the views.
+enum class KmerSet { None, Enumerated, Given };
+inline void set_kmer_set(gk_ctx *c, KmerSet set) {
+    c->have_starts = set != KmerSet::None;
+    c->enumerated = set == KmerSet::Enumerated;
+    c->starts_materialized = set != KmerSet::Enumerated;
+    c->sorted = c->canonical = c->keys_valid = false;
+    drop_order_views(c);
+}
+
+// "A sort of this spec finished": vals[cur] is in the order of max_kmer_len = sort_len (0: None),
+// and keys[cur] belongs to it -- the encoded keys, ranks that only order (keys_are_ranks), or
+// nothing current until ensure_keys re-encodes them from the sorted starts (keys_stale).
+inline void sort_finished(gk_ctx *c, const KeySpec &ks, uint32_t sort_len, bool canonical, bool keys_stale,
+                          bool keys_are_ranks) {
+    c->spec = ks;
+    c->keys_valid = true;
+    c->keys_stale = keys_stale;
+    c->keys_are_ranks = keys_are_ranks;
+    c->sorted = true;
+    c->sort_len = sort_len;
+    c->canonical = canonical;
+}
+
+}  // namespace gkm
+
+// ---------------------------------------------------------------------------------------------
 // launchers (implemented in gkm_encode.hip / gkm_sort.hip / gkm_group.hip)
 // ---------------------------------------------------------------------------------------------
 namespace gkm {
@@ -224,7 +288,7 @@ namespace gkm {
 const char *opt(const char *name);
 
 hipError_t ensure(void **p, uint64_t *cap, uint64_t bytes);
-// large device buffers (gkm_capi.hip): hipMalloc, or an address range mapped from physical
+// large device buffers (gkm_runtime.hip): hipMalloc, or an address range mapped from physical
 // allocations (GKM_VMM_CHUNK_MB); dev_free releases either
 hipError_t dev_alloc(void **p, size_t bytes);
 hipError_t dev_free(void *p);
@@ -290,7 +354,10 @@ int range_own_bits(const KeySpec &ks);
 // by gk_create from lds_rank_check (gkm_partition.h: g_rank_ballot)
 hipError_t rank_mode_msd(int ballot);
 hipError_t rank_mode_sort(int ballot);
-// key / start buffers for n elements and `words` key words (gkm_capi.hip)
+// the lane-order check on the current device, once per process, then its ranking mode set
+// (gkm_rankcheck.hip); a gk_status
+int lds_rank_check(int device);
+// key / start buffers for n elements and `words` key words (gkm_runtime.hip)
 int ensure_elems(gk_ctx *c, uint64_t n, int words);
 // key buffer b alone grown to `words` key words of elem_cap elements (contents not kept)
 int grow_key_buffer(gk_ctx *c, int b, int words);
@@ -360,6 +427,10 @@ __device__ __forceinline__ uint64_t seg_end_of(const uint32_t *__restrict__ seg,
     }
     return (lo + 1 == nseg) ? L - 1 : (uint64_t)seg[lo + 1] - 2;
 }
+// the host's form: last position of segment s
+inline uint64_t seg_last(const uint32_t *seg, uint64_t nseg, uint64_t L, uint64_t s) {
+    return (s + 1 == nseg) ? L - 1 : (uint64_t)seg[s + 1] - 2;
+}
 constexpr uint64_t kMsdKeysMin = 1ull << 20;
 
 // the query calls: gk_lookup, gk_lookup_mismatch, gk_join, gk_screen (these two: gkm_lookup.hip)
@@ -393,11 +464,20 @@ hipError_t scan_u32_exclusive_pair(gk_ctx *c, const uint32_t *in1, uint32_t *out
 hipError_t scan_u32_exclusive_pair_launch(gk_ctx *c, const uint32_t *in1, uint32_t *out1, const uint32_t *in2,
                                           uint32_t *out2, uint64_t n);
 
-// write the lazily enumerated starts into vals[cur] if a reader needs them (gkm_capi.hip)
+// write the lazily enumerated starts into vals[cur] if a reader needs them (gkm_runtime.hip)
 int materialize_starts(gk_ctx *c);
 
-// prefix doubling (gkm_capi.hip)
-hipError_t launch_rank_scatter(gk_ctx *c, const uint32_t *vals, const uint32_t *gid, const uint32_t *gstart, uint64_t n, uint32_t *R);
+// grid of 256-thread workgroups whose threads stride over n items
+inline int grid_of(uint64_t n, int cap = 8192) {
+    uint64_t g = (n + 255) / 256;
+    if (g < 1) g = 1;
+    return (int)(g < (uint64_t)cap ? g : (uint64_t)cap);
+}
+// prefix doubling (gkm_doubling.hip): gk_sort's order of max_kmer_len = M (0: None, the suffix order)
+// by ranks over every position of the sequence; the stable pre-sort of given starts by value, so
+// that ties end in start order (keys[cur] / vals[cur])
+int sort_doubling(gk_ctx *c, uint32_t M);
+int presort_by_start(gk_ctx *c);
 
 }  // namespace gkm
 

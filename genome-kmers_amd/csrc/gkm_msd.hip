@@ -1125,7 +1125,7 @@ struct MsdDriver {
         return sort_tied(g_start, g_len, ng);
     }
 
-    // Prefix doubling (gkm_capi.hip sort_doubling): every run of >= 2 elements of keys[0] / vals[0]
+    // Prefix doubling (gkm_doubling.hip rounds_by_groups): every run of >= 2 elements of keys[0] / vals[0]
     // that `flags` marks as one group (a 1 starts a group) sorted stably by the bkey-bit keys, in
     // place; the members' group heads in c->heads.  Elements outside those groups stay where they
     // are, so a round costs in proportion to the elements still tied, not to n.

@@ -70,7 +70,7 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
 // in order).  A ballot-match takes R + 1 ballots per item and the LDS-mask round trip five LDS
 // instructions (tools/lds_rank_probe.hip: 3.9 vs 0.88 T items/s chip-wide).  The lane order is a
 // hardware property, not an ISA guarantee: gk_create checks it once per device and process
-// (gkm_capi.hip, lds_rank_check) over every digit width the partitions use, and where it does not
+// (gkm_rankcheck.hip, lds_rank_check) over every digit width the partitions use, and where it does not
 // hold switches every partition to the ballot-match ranking below (g_rank_ballot), which relies
 // on nothing but ballots: the same ranks, slower.
 //

@@ -1,5 +1,5 @@
-"""The group pass (gkm_group.hip: group_front, gk_group_hist, gk_group_members; gk_locate in
-gkm_capi.hip) past one 4,096-flag scan tile: prefix groups on the keys and on the bytes, built-in
+"""The group pass (gkm_group.hip: group_front, gk_group_hist, gk_group_members; gk_locate at the
+C boundary, gkm_capi.hip) past one 4,096-flag scan tile: prefix groups on the keys and on the bytes, built-in
 filters on the per-position and the per-k-mer path, histogram bins around the LDS split, yields
 with groups larger than a tile, head masks, the chunked tile-sum scan and every grid-stride loop
 past its grid cap.

@@ -214,7 +214,7 @@ def test_mixed_runs_edges(k, builder, T, canonical, monkeypatch):
 @pytest.mark.parametrize("canonical", [False, True], ids=["fwd", "canon"])
 def test_mixed_runs_k3(canonical, monkeypatch):
     """k = 3: 12-bit 4-bit keys, the class-A keys narrower than the 7-bit L0 digit; the key-range
-    shards take no split below k = 4 (gkm_capi.hip range_split), gk_sort decides by the class-B share"""
+    shards take no split below k = 4 (gkm_shard.hip range_split), gk_sort decides by the class-B share"""
     tag = f"mixed {'canonical' if canonical else 'forward'} k=3"
     for r in reference("runs", 3, T_FLAG, canonical, False):
         sort_and_check(load(r, monkeypatch), r, 3, canonical, False, tag)
