@@ -25,8 +25,10 @@ __global__ __launch_bounds__(256) void rank_scatter_kernel(const uint32_t *__res
 
 // Groups of the current order that may still split: more than one member, and members longer than
 // the h symbols the keys hold.  Members of a group share their first h symbols, so a group whose
-// first member's suffix (to '$' / the end) is at most h long holds equal k-mers and is final --
-// the '$'-terminated tails shared by several contigs, which no doubling round can separate.
+// first member's suffix (to '$' / the end) is shorter than h holds equal k-mers and is final --
+// the '$'-terminated tails shared by several contigs, which no doubling round can separate.  A
+// suffix of exactly h symbols decides nothing: the keys carry no '$' behind the h-th symbol (the
+// ACGT length field stops at h), so the other members may go on, and differ, behind it.
 __global__ __launch_bounds__(256) void unresolved_groups_kernel(const uint32_t *__restrict__ vals,
                                                                 const uint32_t *__restrict__ gstart, uint64_t G,
                                                                 uint64_t n, const uint32_t *__restrict__ seg,
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(256) void unresolved_groups_kernel(const uint32_t *
         const uint64_t b = gstart[g], e = g + 1 < G ? gstart[g + 1] : n;
         if (e - b < 2) continue;
         const uint64_t p = vals[b];
-        if (seg_end_of(seg, nseg, L, p) - p + 1 > h) atomicAdd(count, 1u);
+        if (seg_end_of(seg, nseg, L, p) - p + 1 >= h) atomicAdd(count, 1u);
     }
 }
 

@@ -3,8 +3,10 @@
 // Replaces the reference's serial numba quicksort (kmers.py:1624-1731 -> numba misc/quicksort.py)
 // with a one-sweep-per-digit radix sort:
 //   * one upfront histogram of every 8-bit digit (fused into the encoder on the enumerate path);
-//   * per digit ONE kernel: tile = 256 threads x 16 keys; per-wave 64-lane match via 8 ballots
-//     gives each key its stable rank inside the tile; the tile's digit counts are combined with
+//   * per digit ONE kernel (gkm_onesweep.h): tile = PassShape<W>, 1,024 threads x 12 keys for
+//     one-word keys and 256 x 16 for wider ones; one returning LDS atomic per key on its wave's
+//     digit counter (rank_atomic, gkm_partition.h) gives each key its stable rank inside the wave,
+//     a block scan of the counters its rank inside the tile; the tile's digit counts are combined with
 //     its predecessors' by decoupled look-back over epoch-tagged 64-bit status words (agent-scope
 //     relaxed atomics: the status word is its own flag, no fences); keys are then staged in LDS
 //     in digit order and written out so each digit's run is a coalesced burst.

@@ -16,6 +16,22 @@ builders here put them there on purpose, for a given k and T:
                   two, 32 and 65 homopolymer k-mers) and single IUPAC letters at T - 1, T, across T,
                   2 T and 3 T, at position 0, at the last byte and on both sides of a '$'.
 
+The variable-length and suffix-order sorts (min < max, max None; tests/test_gpu_varlen_edges.py)
+take ``ends``, ``separators`` and ``comb`` at the tiles of their own kernels -- 4,096 (the position
+encoders, the onesweep tile of keys of two or more words, the flag scans), 8,192 (n1 = 8,191 /
+8,192 / 8,193 positions: the doubling's rank width changes) and 12,288 (the onesweep tile of
+one-word keys) -- and two builders for the prefix-doubling rounds, of about 10-13 k bases each:
+
+* ``long_ties``    a poly-A contig of 6,000 bases between two random contigs, a contig of period 8
+                   (ACGTTGCA x 1,000), and a poly-A contig that crosses positions 4,096 and 8,192:
+                   groups that stay tied round after round;
+* ``shared_tails`` contigs that end in the same n bases, one contig that is exactly those n bases
+                   and two contigs that hold them inside, followed by different bases: n = 700, and
+                   n around the seed key's symbols (28, 29, 30 for ACGT data; 15, 16, 17 for IUPAC).
+
+``iupac`` turns the arrays of a builder into their IUPAC variant (about one base in eight becomes a
+letter of RYKMSWBDHVN; every edge stays where it is), given the builder's ``planted`` copies.
+
 Every builder returns a list of ``(label, sba, seg_starts)`` with the arrays as SequenceCollection
 lays them out (contigs joined by '$', seg_starts the first position of every contig), every contig
 holds at least k bases, and every array carries a repeat of 3 k bases twice so that ties occur
@@ -245,4 +261,193 @@ def runs(k, T, lengths=None, splits=None, extras=True):
             s[a] = c
             taken[a] = True
         out.append((p["label"], s, segments_of(s)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# long_ties: contigs whose suffixes stay tied through the prefix-doubling rounds
+# ---------------------------------------------------------------------------------------------
+PERIOD8 = np.frombuffer(b"ACGTTGCA", dtype=np.uint8)
+TIES_REPEAT_AT = 100  # the repeat's offset inside the first and the last (random) contig
+
+
+def long_ties_plan():
+    """[(label, [(kind, bases)])]: the contigs of every array, in order; kind "random", "A" (poly-A)
+    or "period8".  The poly-A contig of "polyA-cross" lies on positions 4,001 .. 8,300: it crosses
+    4,096 and 8,192."""
+    return [("polyA-6000", [("random", 3500), ("A", 6000), ("random", 3500)]),
+            ("period8", [("random", 2000), ("period8", 8000), ("random", 2000)]),
+            ("polyA-cross", [("random", 4000), ("A", 4300), ("random", 2500)])]
+
+
+def _ties_repeat(k):
+    return min(3 * k, 600)
+
+
+def _join(contigs):
+    parts = []
+    for c in contigs:
+        parts += [c, np.array([DOLLAR], dtype=np.uint8)]
+    sba = np.concatenate(parts[:-1])
+    return sba, segments_of(sba)
+
+
+def long_ties(k):
+    """The repeat: min(3 k, 600) bases from offset 100 of the first contig again at offset 100 of the
+    last one (both random)."""
+    assert k <= 2000, "every contig needs k bases"
+    out = []
+    r = _ties_repeat(k)
+    for i, (label, plan) in enumerate(long_ties_plan()):
+        rng = _rng(9, i)
+        contigs = []
+        for kind, n in plan:
+            if kind == "random":
+                contigs.append(_bases(rng, n))
+            elif kind == "A":
+                contigs.append(np.full(n, ord("A"), dtype=np.uint8))
+            else:
+                contigs.append(np.tile(PERIOD8, n // 8))
+        a = TIES_REPEAT_AT
+        contigs[-1][a:a + r] = contigs[0][a:a + r]
+        sba, seg = _join(contigs)
+        out.append((label, sba, seg))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# shared_tails: equal '$'-terminated tails, which no doubling round can separate
+# ---------------------------------------------------------------------------------------------
+TAILS_ACGT = (700, 28, 29, 30)   # 29: the symbols of the ACGT seed key
+TAILS_IUPAC = (700, 15, 16, 17)  # 16: the symbols of the IUPAC seed key
+
+
+def shared_tails_plan(k, tails=TAILS_ACGT):
+    """[dict(label, n, contigs)]: per tail length n the contigs as (bases, offset of the tail or
+    None), in order -- "end" contigs of 2,000, 2,500 and 1,800 bases that end in the tail, the
+    "exact" contig that is the tail alone (left out where n < k), two "inside" contigs of 800 random
+    bases, the tail, one base ('T' in the first, 'C' in the second: the second sorts first although
+    it lies behind) and 799 more random bases, and a random contig of 600 bases.  The first contig
+    ends in the tail, so the tail's lowest position has exactly n bases up to its '$'."""
+    plans = []
+    for n in tails:
+        contigs = [(2000, 2000 - n)]
+        if n >= k:
+            contigs.append((n, 0))
+        contigs += [(800 + n + 800, 800), (800 + n + 800, 800), (2500, 2500 - n), (1800, 1800 - n), (600, None)]
+        plans.append(dict(label=f"tail{n}", n=n, contigs=contigs, before=None))
+    # "lone": one end contig and the two inside contigs, the bases before their tails 'A', 'C', 'G' --
+    # no two suffixes that begin one base before a tail tie, so with n the seed key's symbols the
+    # tails are the only group still tied after the seed sort, and no round repairs what the check
+    # for finished groups lets through; two random contigs fill the array up
+    for n in tails[1:]:
+        contigs = [(2000, 2000 - n), (800 + n + 800, 800), (800 + n + 800, 800), (4500, None), (600, None)]
+        plans.append(dict(label=f"tail{n}-lone", n=n, contigs=contigs, before="ACG"))
+    return plans
+
+
+def shared_tails(k, tails=TAILS_ACGT):
+    """The repeat: the tails themselves."""
+    assert k <= 600, "every contig needs k bases"
+    out = []
+    for p in shared_tails_plan(k, tails):
+        n = p["n"]
+        rng = _rng(10, n) if p["before"] is None else _rng(10, n, 1)
+        tail = _bases(rng, n)
+        contigs, inside, holder = [], 0, 0
+        for length, at in p["contigs"]:
+            c = _bases(rng, length)
+            if at is not None:
+                c[at:at + n] = tail
+                if p["before"]:
+                    c[at - 1] = ord(p["before"][holder])
+                holder += 1
+                if at + n < length:  # an "inside" contig: the base behind the tail
+                    c[at + n] = ord("TC"[inside])
+                    inside += 1
+            contigs.append(c)
+        sba, seg = _join(contigs)
+        out.append((p["label"], sba, seg))
+    return out
+
+
+def tail_positions(k, tails=TAILS_ACGT):
+    """label -> [the tail's first position in every contig that holds it], ascending"""
+    out = {}
+    for p in shared_tails_plan(k, tails):
+        pos, first = [], 0
+        for length, at in p["contigs"]:
+            if at is not None:
+                pos.append(first + at)
+            first += length + 1
+        out[p["label"]] = pos
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the IUPAC variant of a builder's arrays
+# ---------------------------------------------------------------------------------------------
+IUPAC_LETTERS = np.frombuffer(b"RYKMSWBDHVN", dtype=np.uint8)
+
+
+def planted(builder, k, T=None, tails=TAILS_ACGT, tiles=(1, 2)):
+    """label -> (copies, keep) of the arrays of ``builder(k, T)`` (``tiles``, ``tails``: as given to
+    ``separators`` / ``shared_tails``): copies [(source, destination,
+    bases)] are the planted repeats in the order the builder writes them, keep [(first, one past
+    the last)] the ranges whose bases make the array what it is (tied contigs, the base behind an
+    inside tail)."""
+    r = 3 * k
+    out = {}
+    if builder == "ends":
+        for L in end_lengths(k, T):
+            out[f"ends-L{L}"] = ([(T // 4, L - r, r)], [])
+    elif builder == "separators":
+        for m in tiles:
+            for d in separator_offsets(k):
+                at = m * T + d
+                out[f"sep-{m}T{d:+d}"] = ([(at - r, at + 1, r)], [])
+        for o in exact_contig_offsets(k):
+            out[f"exact-T{o:+d}"] = ([(T // 4, T // 2, r), (T // 4, T + o, k)], [])
+    elif builder == "comb":
+        out["comb"] = ([(10 * (COMB_LEN + 1), 40 * (COMB_LEN + 1), min(r, COMB_LEN))], [])
+    elif builder == "long_ties":
+        for label, plan in long_ties_plan():
+            first = [0]
+            for _, n in plan:
+                first.append(first[-1] + n + 1)
+            a = TIES_REPEAT_AT
+            keep = [(first[i], first[i] + n) for i, (kind, n) in enumerate(plan) if kind != "random"]
+            out[label] = ([(a, first[len(plan) - 1] + a, _ties_repeat(k))], keep)
+    elif builder == "shared_tails":
+        plans = {p["label"]: p for p in shared_tails_plan(k, tails)}
+        for label, pos in tail_positions(k, tails).items():
+            n = plans[label]["n"]
+            holders = [(length, at) for length, at in plans[label]["contigs"] if at is not None]
+            keep = [(q + n, q + n + 1) for q, (length, at) in zip(pos, holders) if at + n < length]
+            if plans[label]["before"]:
+                keep += [(q - 1, q) for q in pos]
+            out[label] = ([(pos[0], q, n) for q in pos[1:]], keep)
+    else:
+        raise ValueError(builder)
+    return out
+
+
+def iupac(arrays, plants, share=8):
+    """The arrays with one base in ``share`` (seeded per array) turned into a letter of RYKMSWBDHVN:
+    no '$' and no kept range is touched, and the planted copies are written again from their
+    sources, so every copy still equals its source and every edge lies where it lay."""
+    out = []
+    for i, (label, sba, seg) in enumerate(arrays):
+        copies, keep = plants[label]
+        s = sba.copy()
+        rng = _rng(8, i, len(s))
+        hit = (rng.integers(0, share, len(s)) == 0) & (s != DOLLAR)
+        for lo, hi in keep:
+            hit[lo:hi] = False
+        assert hit.any(), label
+        s[hit] = IUPAC_LETTERS[rng.integers(0, len(IUPAC_LETTERS), int(hit.sum()))]
+        for src, dst, n in copies:
+            s[dst:dst + n] = s[src:src + n]
+        assert (s[sba == DOLLAR] == DOLLAR).all() and ((s == DOLLAR) == (sba == DOLLAR)).all(), label
+        out.append((label + "-iupac", s, seg))
     return out

@@ -228,3 +228,130 @@ def test_builders_are_deterministic():
                   lambda: edgegen.runs(31, 4096), lambda: edgegen.tails(31, 4096)):
         for (la, sa, ga), (lb, sb, gb) in zip(build(), build()):
             assert la == lb and np.array_equal(sa, sb) and np.array_equal(ga, gb)
+
+
+# ---------------------------------------------------------------------------------------------
+# the builders for the variable-length and suffix-order sorts
+# ---------------------------------------------------------------------------------------------
+def longest_run(sba, letter):
+    """(first, length) of the longest run of `letter`"""
+    is_l = np.concatenate([[0], (sba == letter).astype(np.int8), [0]])
+    edges = np.flatnonzero(np.diff(is_l))
+    firsts, lengths = edges[0::2], edges[1::2] - edges[0::2]
+    i = int(lengths.argmax())
+    return int(firsts[i]), int(lengths[i])
+
+
+@pytest.mark.parametrize("k", [1, 3, 5, 40, 125])
+def test_long_ties_layout(k):
+    got = {lab: (s, g) for lab, s, g in edgegen.long_ties(k)}
+    assert list(got) == ["polyA-6000", "period8", "polyA-cross"]
+    want = {"polyA-6000": (13002, [3500, 9501]), "period8": (12002, [2000, 10001]), "polyA-cross": (10802, [4000, 8301])}
+    for label, (sba, seg) in got.items():
+        check_layout(label, sba, seg, k, acgt_only=True)
+        L, dollars = want[label]
+        assert len(sba) == L and 10_000 <= L <= 13_002, label
+        assert np.flatnonzero(sba == DOLLAR).tolist() == dollars, label
+        r = min(3 * k, 600)
+        np.testing.assert_array_equal(sba[100:100 + r], sba[dollars[1] + 101:dollars[1] + 101 + r], err_msg=label)
+    # the poly-A contigs are whole contigs: a '$' (or nothing) on both sides
+    sba, _ = got["polyA-6000"]
+    assert longest_run(sba, ord("A")) == (3501, 6000) and (sba[3501:9501] == ord("A")).all()
+    sba, _ = got["polyA-cross"]
+    first, n = longest_run(sba, ord("A"))
+    assert (first, n) == (4001, 4300)
+    assert first < 4096 < 8192 < first + n  # it crosses both positions
+    assert (first - 1, first + n) == (4000, 8301)  # ... from '$' to '$'
+    sba, _ = got["period8"]
+    np.testing.assert_array_equal(sba[2001:10001], np.tile(np.frombuffer(b"ACGTTGCA", dtype=np.uint8), 1000))
+    # nothing tied is longer than the 6,000 bases the oracle's cost was measured at
+    assert max(n for _, plan in edgegen.long_ties_plan() for kind, n in plan if kind == "A") == 6000
+
+
+@pytest.mark.parametrize("k,tails", [(1, edgegen.TAILS_ACGT), (5, edgegen.TAILS_ACGT), (40, edgegen.TAILS_ACGT),
+                                     (3, edgegen.TAILS_IUPAC)])
+def test_shared_tails_layout(k, tails):
+    assert edgegen.TAILS_ACGT == (700, 28, 29, 30) and edgegen.TAILS_IUPAC == (700, 15, 16, 17)
+    got = edgegen.shared_tails(k, tails)
+    assert [lab for lab, _, _ in got] == [f"tail{n}" for n in tails] + [f"tail{n}-lone" for n in tails[1:]]
+    positions = edgegen.tail_positions(k, tails)
+    for (label, sba, seg), n in zip(got[len(tails):], tails[1:]):
+        # one end contig (the first), the two inside contigs, 'A', 'C', 'G' before their tails
+        check_layout(label, sba, seg, k, acgt_only=True)
+        assert 10_000 <= len(sba) <= 13_000, (label, len(sba))
+        assert [e - b for b, e in contig_bounds(sba, seg)] == [2000, 1600 + n, 1600 + n, 4500, 600], label
+        pos = positions[label]
+        assert pos == [2000 - n, 2001 + 800, 2001 + 1601 + n + 800], label
+        assert all((sba[q:q + n] == sba[pos[0]:pos[0] + n]).all() for q in pos), label
+        assert sba[pos[0] + n] == DOLLAR and [chr(sba[q + n]) for q in pos[1:]] == ["T", "C"], label
+        assert [chr(sba[q - 1]) for q in pos] == ["A", "C", "G"], label
+    for (label, sba, seg), n in zip(got[:len(tails)], tails):
+        check_layout(label, sba, seg, k, acgt_only=True)
+        assert 10_000 <= len(sba) <= 13_000, (label, len(sba))
+        bounds = contig_bounds(sba, seg)
+        lengths = [e - b for b, e in bounds]
+        exact = [n] if n >= k else []
+        assert lengths == [2000] + exact + [1600 + n, 1600 + n, 2500, 1800, 600], label
+        pos = positions[label]
+        assert len(pos) == len(bounds) - 1 and pos == sorted(pos), label
+        tail = sba[pos[0]:pos[0] + n]
+        ends_here, inside = [], []
+        for q in pos:
+            np.testing.assert_array_equal(sba[q:q + n], tail, err_msg=f"{label} at {q}")
+            b, e = next((b, e) for b, e in bounds if b <= q < e)
+            (ends_here if q + n == e else inside).append((q, b, e))
+        # three contigs end in the tail (the first of the array among them: the tail's lowest position
+        # has exactly n bases to its '$'), one is the tail, two hold it inside
+        assert len(ends_here) == 3 + len(exact) and len(inside) == 2, label
+        assert ends_here[0][0] == pos[0] == 2000 - n, label
+        if exact:
+            assert any(q == b and e - b == n for q, b, e in ends_here), label
+        # behind the inside tails: 'T' first, 'C' second -- the later position sorts first
+        assert [chr(sba[q + n]) for q, _, _ in inside] == ["T", "C"] and inside[0][0] < inside[1][0], label
+        assert all(q - b == 800 and e - q - n == 800 for q, b, e in inside), label
+
+
+@pytest.mark.parametrize("builder,k,T", [("ends", 5, 4096), ("ends", 125, 4096), ("separators", 3, 4096),
+                                         ("separators", 65, 4096), ("separators", 1, 12288), ("comb", 3, None),
+                                         ("comb", 125, None), ("long_ties", 3, None), ("shared_tails", 3, None)])
+def test_iupac_variant_keeps_edges_and_copies(builder, k, T):
+    args = (k,) if T is None else (k, T)
+    kw = {"tails": edgegen.TAILS_IUPAC} if builder == "shared_tails" else {}
+    plain = getattr(edgegen, builder)(*args, **kw)
+    plants = edgegen.planted(builder, k, T, **kw)
+    assert set(plants) >= {lab for lab, _, _ in plain}
+    mixed = edgegen.iupac(plain, plants)
+    letters = np.zeros(256, dtype=bool)
+    letters[np.frombuffer(b"RYKMSWBDHVN", dtype=np.uint8)] = True
+    for (label, sba, seg), (mlabel, msba, mseg) in zip(plain, mixed):
+        assert mlabel == label + "-iupac" and len(msba) == len(sba)
+        check_layout(mlabel, msba, mseg, k, acgt_only=False)
+        np.testing.assert_array_equal(msba == DOLLAR, sba == DOLLAR, err_msg=label)
+        changed = msba != sba
+        assert letters[msba[changed]].all() and IS_ACGT[msba[~changed & (msba != DOLLAR)]].all(), label
+        copies, keep = plants[label]
+        assert copies, label
+        for src, dst, n in copies:
+            assert n > 0 and src + n <= dst, label
+            np.testing.assert_array_equal(sba[dst:dst + n], sba[src:src + n], err_msg=f"{label}: planted {src}->{dst}")
+            np.testing.assert_array_equal(msba[dst:dst + n], msba[src:src + n], err_msg=f"{mlabel}: copy {src}->{dst}")
+        for lo, hi in keep:
+            assert lo < hi and not changed[lo:hi].any(), label
+        # about one base in eight outside the kept ranges (binomial: 1/8 +- 5 sigma)
+        free = np.ones(len(sba), dtype=bool)
+        for lo, hi in keep:
+            free[lo:hi] = False
+        for src, dst, n in copies:
+            free[dst:dst + n] = False
+        free &= sba != DOLLAR
+        m = int(free.sum())
+        assert abs(int(changed[free].sum()) - m / 8) <= 5 * np.sqrt(m * 7 / 64), label
+    again = edgegen.iupac(plain, plants)
+    assert all(np.array_equal(a[1], b[1]) for a, b in zip(mixed, again))
+
+
+def test_new_builders_are_deterministic():
+    for build in (lambda: edgegen.long_ties(5), lambda: edgegen.shared_tails(5),
+                  lambda: edgegen.shared_tails(3, edgegen.TAILS_IUPAC)):
+        for (la, sa, ga), (lb, sb, gb) in zip(build(), build()):
+            assert la == lb and np.array_equal(sa, sb) and np.array_equal(ga, gb)
