@@ -1,6 +1,6 @@
 // gkm_capi.hip -- the extern "C" boundary of libgkm.so: lifetime, input, enumerate, gk_sort, the copy,
 // locate and view calls, gk_set_option.  (The shard calls: gkm_shard.hip; gk_rank_mode:
-// gkm_rankcheck.hip; gk_profile_*: gkm_runtime.hip; the query calls: their own files.)
+// gkm_rankcheck.hip; gk_profile_*: gkm_runtime.hip; the query calls and gk_lcp: their own files.)
 //
 // Sort strategies:
 //   direct   max_kmer_len given and the padded key fits 256 bits: encode once, LSD radix sort.
@@ -51,6 +51,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_JOIN_PATH", false},
     // gk_screen (gkm_screen.hip): forced path (bytes | keys), bytes of reads per launch
     {"GKM_SCREEN_PATH", false},     {"GKM_SCREEN_CHUNK", false},
+    // gk_lcp (gkm_lcp.hip): forced path (bytes | keys)
+    {"GKM_LCP_PATH", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)

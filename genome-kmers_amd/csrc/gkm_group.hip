@@ -648,10 +648,14 @@ static int grid_for(uint64_t n, int cap = 8192) {
 using namespace gkm;
 
 // Shared front half of gk_group_hist / gk_group_members: filter, compact, heads, group starts.
-// On success: *cidx_out (nullptr = identity), *count (valid k-mers), *G, group starts in c->idx_b.
+// On success: *cidx_out (nullptr = identity), *count (valid k-mers), *G, group starts in c->idx_b;
+// *heads_out (if asked for; nullptr unless the comparison of step 3 ran or the sort's heads stood in):
+// the head flag of every valid k-mer, which the group starts were selected from.
 static int group_front(gk_ctx *c, int is_sorted, int64_t kmer_len, const gk_filter *filter, const uint32_t **cidx_out,
-                       uint64_t *count, uint64_t *G, int32_t *err_code, uint64_t *err_idx) {
+                       uint64_t *count, uint64_t *G, int32_t *err_code, uint64_t *err_idx,
+                       const uint8_t **heads_out = nullptr) {
     if (err_code) *err_code = 0;
+    if (heads_out) *heads_out = nullptr;
     if (!c->have_starts) return fail(c, GK_E_STATE, "no k-mers: call gk_enumerate first");
     c->unique_valid = false;  // idx_b (the unique output's group starts) is rewritten below
     if (int rc = materialize_starts(c)) return rc;
@@ -782,7 +786,16 @@ static int group_front(gk_ctx *c, int is_sorted, int64_t kmer_len, const gk_filt
     uint64_t g = 0;
     GK_TRY_HIP(c, select_flags(c, heads, cnt, c->idx_b, &g));
     *G = g;
+    if (heads_out) *heads_out = heads;
     return GK_OK;
+}
+
+// the sorted order's groups at kmer_len, every k-mer kept (gkm_lcp.hip's multiplicity track): group
+// starts in c->idx_b, *heads = their flags (c->flags or the sort's own heads), c->idx_a free
+int gkm::group_starts_all(gk_ctx *c, int64_t kmer_len, uint64_t *G, const uint8_t **heads) {
+    const uint32_t *cidx;
+    uint64_t count;
+    return group_front(c, 1, kmer_len, nullptr, &cidx, &count, G, nullptr, nullptr, heads);
 }
 
 extern "C" int gk_group_hist(gk_ctx *c, int is_sorted, int64_t kmer_len, const gk_filter *filter,

@@ -182,6 +182,15 @@ struct gk_ctx {
     bool join_valid = false;
     uint64_t join_n = 0;
 
+    // gk_lcp's view (gkm_lcp.hip; scratch "lcp": uint32[n], lcp[q] = the common prefix of sorted k-mers
+    // q - 1 and q, at most lcp_cap): built by the first call that needs it, rebuilt for a larger cap or
+    // another forced path, dropped with the order's views (drop_order_views)
+    bool lcp_valid = false;
+    bool lcp_bytes = false;    // the byte path built it
+    uint32_t lcp_cap = 0;
+    uint32_t lcp_asked = 0;    // the max_len of the last gk_lcp: what gk_copy_lcp clamps to
+    uint64_t track_len = 0;    // entries of the last position track (scratch "track"), 0: none
+
     // gk_lookup's prefix directory over keys[cur] (gkm_lookup.hip; scratch "lookup_dir"): built by the
     // first key-path lookup after a sort, dropped with the order's views (drop_order_views) and with the
     // key buffers (ensure_elems)
@@ -240,10 +249,10 @@ namespace gkm {
 
 // The order of the k-mers changes: every view cached on it goes -- the group heads, the unique view
 // (and with it gk_join's result, which is valid only while unique_valid is), gk_lookup's directory,
-// and the claim that vals is gk_sort's order of the whole enumeration.  A view added later is
-// dropped here.
+// gk_lcp's array, and the claim that vals is gk_sort's order of the whole enumeration.  A view added
+// later is dropped here.
 inline void drop_order_views(gk_ctx *c) {
-    c->heads_valid = c->unique_valid = c->lookup_dir_valid = c->enum_sorted = false;
+    c->heads_valid = c->unique_valid = c->lookup_dir_valid = c->lcp_valid = c->enum_sorted = false;
 }
 
 // "The k-mer set is now this": no k-mers, the enumeration (its starts written on demand,
@@ -451,6 +460,9 @@ inline bool lookup_keys_usable(const gk_ctx *c) {
 int lookup_build_dir(gk_ctx *c, uint32_t **out);
 
 // group / scan
+// group_front of the sorted order at kmer_len with the keep-all filter (a gk_status): *G groups, their
+// starts in c->idx_b, *heads the head flag of every k-mer (valid until the next group pass or sort)
+int group_starts_all(gk_ctx *c, int64_t kmer_len, uint64_t *G, const uint8_t **heads);
 hipError_t select_flags(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint64_t *count);
 hipError_t select_flags_counts(gk_ctx *c, const uint8_t *flags, uint64_t n, uint32_t *out_idx, uint32_t *out_cnt,
                                uint64_t *count);

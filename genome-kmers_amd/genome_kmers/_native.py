@@ -60,6 +60,7 @@ EXPORTED = (
     "gk_lookup", "gk_copy_strand_range", "gk_lookup_mismatch",
     "gk_join", "gk_copy_join", "gk_device_join", "gk_join_mask",
     "gk_screen",
+    "gk_lcp", "gk_copy_lcp", "gk_device_lcp", "gk_lcp_spectrum", "gk_position_track", "gk_device_track",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
@@ -69,6 +70,9 @@ MISMATCH_BOTH_STRANDS = 1  # GK_MISMATCH_BOTH_STRANDS
 JOIN_KEEP_ABSENT = 1  # GK_JOIN_KEEP_ABSENT
 JOIN_KEEP_PRESENT = 2  # GK_JOIN_KEEP_PRESENT
 SCREEN_BOTH_STRANDS = 1  # GK_SCREEN_BOTH_STRANDS
+NEVER_UNIQUE = 0xFFFFFFFF  # GK_NEVER_UNIQUE
+TRACK_MIN_UNIQUE = 1  # GK_TRACK_MIN_UNIQUE
+TRACK_MULTIPLICITY = 2  # GK_TRACK_MULTIPLICITY
 
 
 class GkFilter(ctypes.Structure):
@@ -172,6 +176,12 @@ _SIGS = {
     "gk_device_join": ([_P, ctypes.POINTER(_P), ctypes.POINTER(_P), _U64P], ctypes.c_int),
     "gk_join_mask": ([_P, ctypes.c_int], ctypes.c_int),
     "gk_screen": ([_P, _U8P, _U64P, ctypes.c_uint64, ctypes.c_uint32, _U32P, _U64P, _U32P], ctypes.c_int),
+    "gk_lcp": ([_P, ctypes.c_uint32, _U64P], ctypes.c_int),
+    "gk_copy_lcp": ([_P, ctypes.c_uint64, _U32P, ctypes.c_uint64], ctypes.c_int),
+    "gk_device_lcp": ([_P, ctypes.POINTER(_P), _U64P], ctypes.c_int),
+    "gk_lcp_spectrum": ([_P, ctypes.c_uint32, _U64P, _U64P], ctypes.c_int),
+    "gk_position_track": ([_P, ctypes.c_int, ctypes.c_uint32, _U32P, ctypes.c_uint64], ctypes.c_int),
+    "gk_device_track": ([_P, ctypes.POINTER(_P), _U64P], ctypes.c_int),
 }
 
 
@@ -689,6 +699,45 @@ class Engine:
                                            _ptr(occurrences, ctypes.c_uint64),
                                            _ptr(wc, ctypes.c_uint32) if per_window else None))
         return n_present, occurrences, wc
+
+    # ---- the LCP array of the sorted order (gk_lcp) -------------------------------------------
+    def lcp(self, max_len: int) -> np.ndarray:
+        """uint32[n]: the common prefix, at most max_len, of every sorted k-mer with its predecessor
+        (gk_lcp builds or reuses the device view, gk_copy_lcp copies it clamped to max_len)."""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.gk_lcp(self.ctx, int(max_len), ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(self.lib.gk_copy_lcp(self.ctx, 0, _ptr(out, ctypes.c_uint32), n.value))
+        return out
+
+    def device_lcp(self):
+        """(device pointer of the view uint32*, n) of the last lcp (gk_device_lcp)."""
+        p, n = _P(), ctypes.c_uint64()
+        self._check(self.lib.gk_device_lcp(self.ctx, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def lcp_spectrum(self, max_len: int):
+        """(distinct int64[max_len + 1], unique int64[max_len + 1]) indexed by k (gk_lcp_spectrum)."""
+        distinct = np.zeros(int(max_len) + 1, dtype=np.uint64)
+        unique = np.zeros(int(max_len) + 1, dtype=np.uint64)
+        self._check(self.lib.gk_lcp_spectrum(self.ctx, int(max_len), _ptr(distinct, ctypes.c_uint64),
+                                             _ptr(unique, ctypes.c_uint64)))
+        return distinct.astype(np.int64), unique.astype(np.int64)
+
+    def position_track(self, kind: int, length: int, sba_len: int) -> np.ndarray:
+        """uint32[sba_len] in sequence order (gk_position_track): kind = TRACK_MIN_UNIQUE (length: the
+        cap) or TRACK_MULTIPLICITY (length: kmer_len, 0 = the sort length)."""
+        out = np.zeros(int(sba_len), dtype=np.uint32)
+        self._check(self.lib.gk_position_track(self.ctx, int(kind), int(length), _ptr(out, ctypes.c_uint32),
+                                               int(sba_len)))
+        return out
+
+    def device_track(self):
+        """(device pointer uint32*, sba_len) of the last position track (gk_device_track)."""
+        p, n = _P(), ctypes.c_uint64()
+        self._check(self.lib.gk_device_track(self.ctx, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
 
     # ---- multi-GPU shards (genome_kmers.distributed) ------------------------------------------
     def shard_bucket_bits(self) -> int:

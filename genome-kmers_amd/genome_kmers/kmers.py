@@ -32,6 +32,7 @@ from . import _native
 from .sequence_collection import SequenceCollection
 
 DOLLAR = ord("$")
+NEVER_UNIQUE = _native.NEVER_UNIQUE  # min_unique_lengths: not unique at any length up to max_len
 
 # Kmers.screen's result: per read the number of windows, of windows present in the index and the sum of
 # the windows' counts; with per_window=True also the count per byte position and the reads' offsets
@@ -934,6 +935,76 @@ class Kmers:
         if per_window:
             return ScreenResult(n_windows, n_present, occurrences, wc, off)
         return ScreenResult(n_windows, n_present, occurrences)
+
+    # ---- the LCP array, the spectrum and the position tracks (no reference counterpart) ---------
+    def _lcp_checks(self, what, length, name="max_len"):
+        """The preconditions of gk_lcp / gk_lcp_spectrum / gk_position_track, checked on the host
+        before any device call; returns the length to pass on (None resolved to max_kmer_len)."""
+        if not self._is_sorted:
+            raise AssertionError(f"The kmers must be sorted when calling {what}")
+        if self.kmer_source_strand != "forward":
+            raise ValueError(f"{what} needs kmer_source_strand 'forward' ({self.kmer_source_strand!r})")
+        if length is None:
+            if self.max_kmer_len is None:
+                raise ValueError(f"{what} needs {name} when max_kmer_len is None (the suffix order has no "
+                                 f"length of its own; {name}: None)")
+            return self.max_kmer_len
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)):
+            raise ValueError(f"{name} must be an int >= 1 ({name}: {length!r})")
+        if length < 1:
+            raise ValueError(f"{name} ({length}) must be >= 1")
+        if self.max_kmer_len is not None and length > self.max_kmer_len:
+            raise ValueError(f"{name} ({length}) is greater than max_kmer_len ({self.max_kmer_len})")
+        return int(length)
+
+    def lcp(self, max_len: Union[int, None] = None) -> np.ndarray:
+        """The longest common prefix of every sorted k-mer with its predecessor (gk_lcp): uint32, in
+        sorted order, ``lcp[0] == 0``.
+
+        ``lcp[q]`` is the largest k in 0..``max_len`` at which k-mers q - 1 and q compare equal under
+        the reference's comparison (kmers.py:306-397) at ``kmer_len = k``; two k-mers that end at a
+        '$' after the same bases are equal at every length (``max_len``).  So the groups of
+        ``get_kmer_group_counts(k)`` start where ``lcp < k``, for every k up to ``max_len`` at once.
+        ``max_len`` defaults to max_kmer_len and may not exceed it.  When max_kmer_len is None (the
+        suffix order) ``max_len`` must be given: inside long repeats the comparison costs up to
+        ``max_len`` steps per pair of neighbours.  The array stays on the device as a view of the
+        sorted order (a later call with a smaller ``max_len`` is served from it); not available
+        after sort(canonical=True), where k-mers have no prefixes."""
+        cap = self._lcp_checks("lcp", max_len)
+        self._sync_device()
+        return self._engine.lcp(cap)
+
+    def kmer_spectrum(self, max_len: Union[int, None] = None) -> tuple:
+        """``(distinct, unique)``: two int64 arrays indexed by k = 1..``max_len`` (entry 0 unused and 0),
+        the number of distinct k-mers of length k and the number of those that occur once -- what
+        ``get_kmer_group_counts(k)`` gives one k at a time -- from one pass over the LCP array
+        (gk_lcp_spectrum).  ``max_len`` as in ``lcp``."""
+        cap = self._lcp_checks("kmer_spectrum", max_len)
+        self._sync_device()
+        return self._engine.lcp_spectrum(cap)
+
+    def min_unique_lengths(self, max_len: Union[int, None] = None) -> np.ndarray:
+        """uint32[len(sba)] in sequence order: at the start of every k-mer the shortest length at which
+        the k-mer that starts there occurs nowhere else, ``NEVER_UNIQUE`` where that is above
+        ``max_len``, 0 where no k-mer of the current set starts ('$', contig tails shorter than
+        min_kmer_len, positions outside assigned start indices).  ``max_len`` as in ``lcp``."""
+        cap = self._lcp_checks("min_unique_lengths", max_len)
+        self._sync_device()
+        return self._engine.position_track(_native.TRACK_MIN_UNIQUE, cap, len(self.seq_coll.forward_sba))
+
+    def multiplicity_track(self, kmer_len: Union[int, None] = None) -> np.ndarray:
+        """uint32[len(sba)] in sequence order: at the start of every k-mer the number of k-mers equal
+        to it at ``kmer_len`` (a mappability track), 0 where no k-mer of the current set starts.
+        ``kmer_len`` defaults to max_kmer_len (None on a suffix order: whole suffixes up to '$');
+        after sort(canonical=True) only max_kmer_len, where a k-mer and its reverse complement are
+        one group."""
+        if kmer_len is not None:
+            kmer_len = self._lcp_checks("multiplicity_track", kmer_len, name="kmer_len")
+        elif not self._is_sorted:
+            raise AssertionError("The kmers must be sorted when calling multiplicity_track")
+        self._sync_device()
+        return self._engine.position_track(_native.TRACK_MULTIPLICITY, kmer_len or 0,
+                                           len(self.seq_coll.forward_sba))
 
     def get_encoded_kmers(self) -> np.ndarray:
         """Encoded keys of the sorted k-mers, one row per k-mer."""

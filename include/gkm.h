@@ -415,6 +415,52 @@ int gk_join_mask(gk_ctx *a, int keep);
 int gk_screen(gk_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint64_t nseq, uint32_t flags,
               uint32_t *n_present, uint64_t *occurrences, uint32_t *window_count);
 
+/* The LCP array of the sorted order and what is read off it (no reference routine: the reference
+ * answers for one length per call; equality is its compare_sba_kmers_lexicographically, kmers.py:306-397).
+ * For a forward (non-canonical) sort and a cap max_len >= 1: lcp[q] (q >= 1) = the largest k in
+ * 0..max_len at which sorted k-mers q - 1 and q compare equal at kmer_len = k; lcp[0] = 0, and lcp[n] = 0
+ * wherever a successor is needed.  A '$' on both sides at the same offset, after equal bytes, means
+ * equal at every length (lcp = max_len); a '$' on one side ends the common prefix.  So for every
+ * 1 <= k <= max_len the group head at k is exactly lcp[q] < k, and a k-mer cut short after len bases
+ * has lcp in [0, len) or equal to max_len.
+ * gk_lcp builds the array as a view of the sorted order (device uint32[*n], like the unique view; dropped
+ * by a sort, new starts or a new sequence) or reuses it: a view built for a larger max_len serves a
+ * smaller one by clamping, a larger max_len rebuilds it.  After a bounded sort max_len may not exceed
+ * the sort length; after a sort with max_kmer_len None it is the caller's choice, and the byte
+ * comparison costs up to max_len steps per pair inside long repeats.  Two paths with the same answers:
+ * the encoded keys where they decide prefixes (direct keys without a length field: XOR, count leading
+ * zeros), else the sequence bytes (bounded variable-length 2-bit keys, rank keys, None, fewer than two
+ * k-mers); GKM_LCP_PATH = bytes | keys (gk_set_option) forces one, keys where it does not apply:
+ * GK_E_UNSUPPORTED.
+ * gk_copy_lcp: entries [offset, offset + count) of the view, clamped to the max_len of the last gk_lcp.
+ * gk_device_lcp: the device array; its entries are capped at the cap the view was built with, which is
+ * >= the last max_len (a reader clamps).  Both: GK_E_STATE without a valid view.
+ * gk_lcp_spectrum: distinct[k] = #{q : lcp[q] < k} (the distinct k-mers of length k) and
+ * unique[k] = #{q : max(lcp[q], lcp[q + 1]) < k} (those that occur once), k = 1..max_len, entry 0
+ * unused and 0; both arrays hold max_len + 1 entries.  k-mers cut short by a contig end count as
+ * gk_group_hist counts them with the keep-all filter.  One pass over the view, built if needed.
+ * gk_position_track: a uint32[sba_len] track in sequence order, 0 where no k-mer of the current set
+ * starts ('$', contig tails, positions below min_kmer_len, positions outside given starts); sba_len must
+ * be the sequence's length; dst may be NULL (the track stays on the device: gk_device_track, the last
+ * track built, valid until the next gk_position_track).
+ *   GK_TRACK_MIN_UNIQUE    len = the cap: track[starts[q]] = max(lcp[q], lcp[q + 1]) + 1, the shortest
+ *                          length at which k-mer q is unique, or GK_NEVER_UNIQUE when that exceeds len.
+ *   GK_TRACK_MULTIPLICITY  len = kmer_len (0: the sort length): track[starts[q]] = the size of q's
+ *                          group at kmer_len.  At the sort length it also works after GK_SORT_CANONICAL.
+ * All synchronise the stream.  GK_E_ARG: a null context or array, max_len == 0 or above 2^24, max_len or
+ * kmer_len above the sort length of a bounded sort, an unknown kind, a wrong sba_len; GK_E_STATE: no
+ * sequence, or not sorted; GK_E_UNSUPPORTED: a canonical order (no prefixes) for gk_lcp, the
+ * spectrum, GK_TRACK_MIN_UNIQUE and a multiplicity at another length than the sort's. */
+#define GK_NEVER_UNIQUE 0xFFFFFFFFu
+#define GK_TRACK_MIN_UNIQUE 1
+#define GK_TRACK_MULTIPLICITY 2
+int gk_lcp(gk_ctx *ctx, uint32_t max_len, uint64_t *n);
+int gk_copy_lcp(gk_ctx *ctx, uint64_t offset, uint32_t *dst, uint64_t count);
+int gk_device_lcp(gk_ctx *ctx, void **lcp, uint64_t *n);
+int gk_lcp_spectrum(gk_ctx *ctx, uint32_t max_len, uint64_t *distinct, uint64_t *unique);
+int gk_position_track(gk_ctx *ctx, int kind, uint32_t len, uint32_t *dst, uint64_t sba_len);
+int gk_device_track(gk_ctx *ctx, void **track, uint64_t *sba_len);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
