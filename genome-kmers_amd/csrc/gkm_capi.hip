@@ -336,18 +336,19 @@ static int sort_direct(gk_ctx *c, const KeySpec &ks) {
     if (rc != GK_OK) return rc;
     if (msd) {
         // a mixed sba (N runs, IUPAC letters): ACGT-only k-mers on 2-bit keys, the rest apart
-        bool split = false;
+        bool split = false, keys_final = false;
         if (!c->acgt) {
-            rc = split_sort(c, ks, &split);
+            rc = split_sort(c, ks, &split, &keys_final);
             if (rc != GK_OK) return rc;
         }
-        if (!split) rc = prefetch_matches(c, ks) ? msd_sort_prefetched(c, ks) : msd_sort(c, ks);
+        if (!split)
+            rc = prefetch_matches(c, ks, c->n) ? msd_sort_prefetched(c, ks, c->n, false, &keys_final)
+                                               : msd_sort(c, ks, c->n, false, &keys_final);
         pre_drop(c);
         if (rc != GK_OK) return rc;
-        // a one-word MSD sort leaves the sorted keys in keys[0]; the split sort (2-bit class-A keys
-        // under a 4-bit key spec) and multi-word phases leave them to ensure_keys
-        sort_finished(c, ks, (uint32_t)ks.symbols, ks.canonical != 0,
-                      /*keys_stale*/ split ? !c->split_keys_final : !c->msd_keys_final, /*keys_are_ranks*/ false);
+        // the sort that ran says whether it left the sorted keys (a one-word MSD sort: in keys[0]); else ensure_keys
+        sort_finished(c, ks, (uint32_t)ks.symbols, ks.canonical != 0, /*keys_stale*/ !keys_final,
+                      /*keys_are_ranks*/ false);
         return GK_OK;
     }
     bool hist_ready = false;

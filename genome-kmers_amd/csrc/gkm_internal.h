@@ -66,6 +66,13 @@ inline KeySpec key_spec(int bits, uint64_t symbols, int lenbits, int min_len) {
     ks.words = (int)((tb + 63) / 64);
     return ks;
 }
+// the 2-bit spec of a mixed sba's ACGT-only k-mers under the 4-bit spec ks (gkm_split.hip, key-range shards)
+inline KeySpec acgt_spec(const KeySpec &ks) {
+    KeySpec a = key_spec(2, ks.symbols, ks.lenbits, ks.min_len);
+    a.canonical = ks.canonical;
+    a.acgt_only = 1;
+    return a;
+}
 inline int bit_width(uint64_t v) {
     int b = 0;
     while (v) {
@@ -113,10 +120,7 @@ struct gk_ctx {
     uint32_t sort_len = 0;     // max_kmer_len of the last sort (0 = None)
     bool canonical = false;    // the last sort ordered canonical k-mers (GK_SORT_CANONICAL)
     bool keys_valid = false;   // keys[cur] encode the k-mers of vals[cur] (sort order)
-    bool msd_keys_final = false;  // the last MSD sort wrote its (one-word) keys in sorted order
-    bool msd_force_keys = false;  // split_sort: the class-A MSD (acgt_only) writes its final keys too
-    bool split_keys_final = false;  // the last split sort wrote the final (4-bit) keys in sorted order
-    bool keys_stale = false;   // ... once re-encoded from vals[cur]: the MSD sort does not keep them (ensure_keys)
+    bool keys_stale = false;   // ... once ensure_keys re-encodes them from vals[cur]: the sort reported no final keys
     bool enum_sorted = false;  // vals = gk_sort's order of ALL enumerated k-mers (fixed length): ensure_keys
                                // may gather the keys through a table in enumeration order
     bool keys_are_ranks = false;
@@ -281,6 +285,27 @@ inline void sort_finished(gk_ctx *c, const KeySpec &ks, uint32_t sort_len, bool 
     c->canonical = canonical;
 }
 
+// For one scope, radix_sort's and ensure_elems' operands: the count n and the pair ks / vs at index cur, or the
+// count alone (ensure_elems may replace the context's buffers).  The earlier values return on every way out.
+struct ScopedOperands {
+    gk_ctx *const c;
+    const bool pair;
+    const uint64_t n;
+    uint64_t *const k[2];
+    uint32_t *const v[2];
+    const int cur;
+    ScopedOperands(gk_ctx *c_, uint64_t n_, uint64_t *const *ks = nullptr, uint32_t *const *vs = nullptr, int cur_ = 0)
+        : c(c_), pair(ks), n(c_->n), k{c_->keys[0], c_->keys[1]}, v{c_->vals[0], c_->vals[1]}, cur(c_->cur) {
+        c->n = n_;
+        if (pair) c->keys[0] = ks[0], c->keys[1] = ks[1], c->vals[0] = vs[0], c->vals[1] = vs[1], c->cur = cur_;
+    }
+    ScopedOperands(const ScopedOperands &) = delete;  // (a copy would put the old values back twice)
+    ~ScopedOperands() {
+        c->n = n;
+        if (pair) c->keys[0] = k[0], c->keys[1] = k[1], c->vals[0] = v[0], c->vals[1] = v[1], c->cur = cur;
+    }
+};
+
 }  // namespace gkm
 
 // ---------------------------------------------------------------------------------------------
@@ -324,8 +349,10 @@ inline void scratch_release(gk_ctx *c, const char *name) {
 }
 // re-encode keys[cur] from vals[cur] when the sort left them stale (gk_ctx::keys_stale)
 int ensure_keys(gk_ctx *c);
-// MSD sort of fixed-length keys from the enumerated positions (gkm_msd.hip)
-int msd_sort(gk_ctx *c, const KeySpec &ks);
+// The sort entry points say in *keys_final (if not null) whether keys[cur] holds the sorted order's final keys (its
+// negation is sort_finished's keys_stale); acgt_keys: an acgt_only sort writes them too (split_sort's wish).
+// MSD sort of fixed-length keys from the n enumerated positions (gkm_msd.hip)
+int msd_sort(gk_ctx *c, const KeySpec &ks, uint64_t n, bool acgt_keys, bool *keys_final);
 // fixed-length sort of a mixed-alphabet sba: ACGT-only k-mers by the 2-bit MSD, the others by
 // 4-bit keys, merged (gkm_split.hip); *used = false when the split does not pay (caller falls back)
 // key-range shards of a mixed sba (gk_shard_sort_range): ACGT-only k-mers whose 2-bit top-7-bit
@@ -341,7 +368,7 @@ struct SplitRange {
     const uint32_t *rest = nullptr, *runs = nullptr;
     uint64_t n_rest = 0, n_runs = 0;
 };
-int split_sort(gk_ctx *c, const KeySpec &ks, bool *used, const SplitRange *rg = nullptr);
+int split_sort(gk_ctx *c, const KeySpec &ks, bool *used, bool *keys_final, const SplitRange *rg = nullptr);
 int split_shard_class_b(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, const std::vector<uint32_t> &bins,
                         int pns, uint32_t homo_w16, uint64_t *hist, std::vector<uint32_t> *rest,
                         std::vector<uint32_t> *runs);
@@ -350,13 +377,14 @@ int split_shard_class_b(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
 int msd_shard_partition(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uint64_t *kout, uint32_t *vout,
                         uint64_t cap, uint64_t *hist, uint64_t *count);
 int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint32_t *vin, const uint64_t *poff,
-                   const uint64_t *plen, const uint32_t *pbucket, uint32_t np);
+                   const uint64_t *plen, const uint32_t *pbucket, uint32_t np, bool *keys_final);
 int msd_radix_bits();
 // key-range shards (gkm_msd.hip): the L0 digit histogram (*bits = digit width) of the k-mers
 // starting in [lo, hi); the sort of the k-mers of the whole sba whose L0 digit is in
 // [digit_lo, digit_hi) into keys[0] / vals[0] (c->n = *n_kept)
 int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uint64_t *hist, int *bits);
-int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t digit_hi, uint64_t *n_kept);
+int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t digit_hi, bool acgt_keys, uint64_t *n_kept,
+                   bool *keys_final);
 // width of the key-range ownership digits (gk_shard_histogram's bins: 1 << width)
 int range_own_bits(const KeySpec &ks);
 // partition ranking of each code object: lane-ordered LDS atomics (0) or ballot-match (1), set
@@ -390,9 +418,9 @@ void xfer_release(gk_ctx *c);
 int prefetch_plan(gk_ctx *c, uint64_t len, L0Prefetch **out);
 int prefetch_launch(gk_ctx *c, L0Prefetch *pf, uint64_t landed);
 int prefetch_finish(gk_ctx *c, L0Prefetch *pf, bool ok);
-// gk_sort(k) of the whole enumeration when the prefetched L0 is valid for its key spec
-bool prefetch_matches(const gk_ctx *c, const KeySpec &ks);
-int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks);
+// gk_sort(k) of the whole enumeration (n k-mers) when the prefetched L0 is valid for its key spec
+bool prefetch_matches(const gk_ctx *c, const KeySpec &ks, uint64_t n);
+int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks, uint64_t n, bool acgt_keys, bool *keys_final);
 inline void pre_drop(gk_ctx *c) { c->pre_valid = false; }
 
 // encode

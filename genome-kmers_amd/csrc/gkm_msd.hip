@@ -215,6 +215,7 @@ struct MsdDriver {
     // final keys: the finishing kernels also write every key to keys[0], so a one-word sort ends
     // with sorted keys + starts + heads in HBM (no re-encode by gather afterwards)
     int wkeys = 0;
+    bool acgt_keys = false;  // the caller of an acgt_only sort wants its final keys too (split_sort)
     // the L0 passes' arguments (l0_count fills them in; pk_code / pk_dol, the packed sequence, are set
     // beforehand by use_resident_pack) and tiles; key-range shards: the ownership digit range
     // [own_lo, own_lo + own_span) is kept
@@ -305,15 +306,15 @@ struct MsdDriver {
     // The set-up of a sort entry point (all but msd_sort_groups, which sorts inside another sort's
     // product and neither writes final keys for the context nor takes packed-pair levels):
     //   B          the bits of the first key word (key_bits: keys that are not made of symbols)
-    //   wkeys      a one-word sort ends with its keys final in keys[0] (c->msd_keys_final) -- but the
-    //              ACGT-only class of a mixed sba only where the split sort asks for them
+    //   wkeys      a one-word sort ends with its keys final in keys[0] (*keys_final tells the entry point's caller)
+    //              -- but the ACGT-only class of a mixed sba only where the split sort asks (acgt_keys)
     //   allow_c79  packed-pair levels where the bits fit
     // then the total timer, and the lists for n elements (kInitLater: n is not known yet)
     static constexpr uint64_t kInitLater = ~0ull;
-    int begin(uint64_t n_, int key_bits = 0) {
+    int begin(uint64_t n_, bool *keys_final, int key_bits = 0) {
         B = key_bits ? key_bits : ks.bits * std::min(ks.symbols, symbols_per_word());
-        wkeys = (phases() == 1 && (!ks.acgt_only || c->msd_force_keys)) ? 1 : 0;
-        c->msd_keys_final = wkeys != 0;
+        wkeys = (phases() == 1 && (!ks.acgt_only || acgt_keys)) ? 1 : 0;
+        if (keys_final) *keys_final = wkeys != 0;
         allow_c79 = true;
         timer_begin(c, "msd_total", &total_slot);
         return n_ != kInitLater ? init(n_) : GK_OK;
@@ -770,7 +771,7 @@ struct MsdDriver {
     // they hold all of them and are never uniform (`elems`: the level's output, or its input where
     // the decision comes before the classify's read-back)
     bool few_big_elems(int level, uint64_t elems) const {
-        return level >= 1 && elems * 64 <= std::max<uint64_t>(c->n, 1);
+        return level >= 1 && elems * 64 <= std::max<uint64_t>(n, 1);
     }
 
     // Which input format a level writing `out` reads as it is; any other input goes back to (key,
@@ -1399,9 +1400,10 @@ struct MsdDriver {
 
 // The enumerated k-mers of the whole sequence (gk_sort's fixed-length path, k <= 64), in one-word
 // phases (MsdDriver::phases).
-int msd_sort(gk_ctx *c, const KeySpec &ks) {
+int msd_sort(gk_ctx *c, const KeySpec &ks, uint64_t n, bool acgt_keys, bool *keys_final) {
     MsdDriver d(c, ks);
-    int rc = d.begin(c->n);
+    d.acgt_keys = acgt_keys;
+    int rc = d.begin(n, keys_final);
     if (rc != GK_OK) return rc;
     if (d.phases() == 1) d.enable_wide_l0();
     // canonical 2-bit keys with a full 64-bit first word (k >= 32; C5): an 8-bit L0 leaves 48 bits
@@ -1413,7 +1415,7 @@ int msd_sort(gk_ctx *c, const KeySpec &ks) {
     uint64_t found = 0;
     rc = d.l0_count(0, c->sba_len, 0, 0xFFFFFFFFu, &found);  // all digits owned
     if (rc != GK_OK) return rc;
-    if (found != c->n) return fail(c, GK_E_HIP, "msd: k-mer count differs from the enumeration");
+    if (found != n) return fail(c, GK_E_HIP, "msd: k-mer count differs from the enumeration");
     int in = 0;
     rc = d.l0_start(found, &in);
     if (rc != GK_OK) return rc;
@@ -1462,10 +1464,10 @@ static KeySpec hint_spec(uint32_t k) {
     return ks;
 }
 
-bool prefetch_matches(const gk_ctx *c, const KeySpec &ks) {
+bool prefetch_matches(const gk_ctx *c, const KeySpec &ks, uint64_t n) {
     return c->pre_valid && c->enumerated && ks.bits == 2 && ks.symbols == (int)c->pre_k &&
            ks.min_len == ks.symbols && ks.words == 1 && ks.lenbits == 0 && !ks.canonical &&
-           c->n + ks.symbols - 1 <= c->sba_len;  // (acgt_only: the class A of a mixed sba, gkm_split.hip)
+           n + ks.symbols - 1 <= c->sba_len;  // (acgt_only: the class A of a mixed sba, gkm_split.hip)
 }
 
 int prefetch_plan(gk_ctx *c, uint64_t len, L0Prefetch **out) {
@@ -1606,11 +1608,13 @@ int prefetch_finish(gk_ctx *c, L0Prefetch *p, bool ok) {
 }
 
 // gk_sort(k) after a prefetched L0: the regions' buckets are the pieces of the first level
-int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks) {
+int msd_sort_prefetched(gk_ctx *c, const KeySpec &ks, uint64_t n, bool acgt_keys, bool *keys_final) {
     c->pre_valid = false;  // consumed
     MsdDriver d(c, ks);
-    if (d.width(0) != c->pre_w0 || d.width(1) != c->pre_w1) return msd_sort(c, ks);  // (widths changed)
-    int rc = d.begin(c->n, ks.total_bits);  // (one word: prefetch_matches)
+    if (d.width(0) != c->pre_w0 || d.width(1) != c->pre_w1)  // (widths changed)
+        return msd_sort(c, ks, n, acgt_keys, keys_final);
+    d.acgt_keys = acgt_keys;
+    int rc = d.begin(n, keys_final, ks.total_bits);  // (one word: prefetch_matches)
     if (rc != GK_OK) return rc;
     const uint32_t R = 1u << c->pre_w0, nreg = c->pre_regions;
     uint32_t *pieces;
@@ -1665,10 +1669,10 @@ int msd_shard_partition(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
 
 // multi-GPU receive side: sort n received k-mers (buckets as pieces) into keys[0] / vals[0]
 int msd_shard_sort(gk_ctx *c, const KeySpec &ks, const uint64_t *kin, const uint32_t *vin, const uint64_t *poff,
-                   const uint64_t *plen, const uint32_t *pbucket, uint32_t np) {
+                   const uint64_t *plen, const uint32_t *pbucket, uint32_t np, bool *keys_final) {
     MsdDriver d(c, ks);
     d.wsched[0] = kGR;  // pieces are kGR-bit buckets
-    int rc = d.begin(c->n);
+    int rc = d.begin(c->n, keys_final);
     if (rc != GK_OK) return rc;
     if (!kin) {
         // starts only (GK_SHARD_STARTS_ONLY): every received k-mer's key from the rank's own packed copy
@@ -1723,7 +1727,7 @@ int msd_sort_keys(gk_ctx *c, int total_bits) {
         for (int l = 0; l < kMaxLevels; ++l) d.wsched[l] = l < L ? w : kGR;
     }
     const int in = c->cur;
-    int rc = d.begin(c->n, total_bits);  // (one word of up to 8 "symbols": the keys end final in keys[0])
+    int rc = d.begin(c->n, nullptr, total_bits);  // (one word of up to 8 "symbols": the keys end final in keys[0])
     if (rc != GK_OK) return rc;
     uint32_t *one;
     GK_TRY_HIP(c, scratch(c, "keys_bucket", 2, &one));
@@ -1814,12 +1818,14 @@ int msd_l0_histogram(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, uin
     return GK_OK;
 }
 
-int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t digit_hi, uint64_t *n_kept) {
+int msd_sort_range(gk_ctx *c, const KeySpec &ks, uint32_t digit_lo, uint32_t digit_hi, bool acgt_keys, uint64_t *n_kept,
+                   bool *keys_final) {
     MsdDriver d(c, ks);
+    d.acgt_keys = acgt_keys;
     d.wsched[0] = range_width(ks);
     // (packed-pair levels where the bits fit: the first level from the select's pieces has 55 bits
     // left at C3, its L1 writes the pairs)
-    int rc = d.begin(MsdDriver::kInitLater);  // (the lists once the select or the count has found n)
+    int rc = d.begin(MsdDriver::kInitLater, keys_final);  // (the lists once the select or the count has found n)
     if (rc != GK_OK) return rc;
     GK_TRY_HIP(c, msd_tables());
     const uint64_t L = c->sba_len;

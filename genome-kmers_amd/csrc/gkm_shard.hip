@@ -42,13 +42,6 @@ extern "C" int gk_shard_partition(gk_ctx *c, uint64_t lo, uint64_t hi, uint32_t 
 // the byte-order interval those digits bound.  k < 4: plain 4-bit digits.
 static bool range_split(gk_ctx *c, const KeySpec &ks) { return !c->acgt && ks.bits == 4 && ks.symbols >= 4; }
 
-static KeySpec acgt_spec(const KeySpec &ks) {
-    KeySpec a = key_spec(2, ks.symbols, ks.lenbits, ks.min_len);
-    a.canonical = ks.canonical;
-    a.acgt_only = 1;
-    return a;
-}
-
 // the 4-bit code of the first ceil(ob / 2) symbols of the smallest ACGT k-mer with top-ob-bit
 // digit d (an odd width ends in a half symbol: A or G by the digit's low bit); a range from digit
 // 0 has no lower bound, a range to digit 1 << ob no upper one
@@ -134,6 +127,7 @@ static int shard_sort_range_impl(gk_ctx *c, uint32_t k, uint32_t flags, uint32_t
     if (rc != GK_OK) return rc;
     c->min_k = k;
     set_kmer_set(c, KmerSet::Given);
+    bool used = false, keys_final = false;
     if (range_split(c, ks)) {  // mixed sba: ACGT-only k-mers by 2-bit digit, the rest by prefix
         const int ob = range_own_bits(acgt_spec(ks));
         SplitRange rg{digit_lo, digit_hi, range_prefix(digit_lo, true, ob), range_prefix(digit_hi, false, ob), (ob + 1) / 2};
@@ -142,18 +136,15 @@ static int shard_sort_range_impl(gk_ctx *c, uint32_t k, uint32_t flags, uint32_t
         rg.n_rest = n_rest;
         rg.runs = runs;
         rg.n_runs = n_runs;
-        bool used = false;
-        rc = split_sort(c, ks, &used, &rg);
+        rc = split_sort(c, ks, &used, &keys_final, &rg);
         if (rc == GK_OK && !used) rc = fail(c, GK_E_HIP, "key-range split sort not applicable");
         *n_kept = c->n;
     } else {
-        rc = msd_sort_range(c, ks, digit_lo, digit_hi, n_kept);
+        rc = msd_sort_range(c, ks, digit_lo, digit_hi, false, n_kept, &keys_final);
     }
     if (rc != GK_OK) return rc;
-    // (keys_stale: see sort_direct, gkm_capi.hip)
-    sort_finished(c, ks, k, ks.canonical != 0,
-                  /*keys_stale*/ c->n > 0 && (range_split(c, ks) ? !c->split_keys_final : !c->msd_keys_final),
-                  /*keys_are_ranks*/ false);
+    // (keys_stale: what the sort just called reported, as in sort_direct, gkm_capi.hip; no k-mers, no keys)
+    sort_finished(c, ks, k, ks.canonical != 0, /*keys_stale*/ c->n > 0 && !keys_final, /*keys_are_ranks*/ false);
     return GK_OK;
 }
 
@@ -188,14 +179,15 @@ extern "C" int gk_shard_sort(gk_ctx *c, const uint64_t *d_keys, const uint32_t *
     c->n = n;
     c->min_k = k;
     set_kmer_set(c, KmerSet::Given);
+    bool keys_final = false;
     if (n > 0) {
         rc = msd_shard_sort(c, ks, starts_only ? nullptr : d_keys, d_starts, h_piece_off, h_piece_len, h_piece_bucket,
-                            npieces);
+                            npieces, &keys_final);
         if (rc != GK_OK) return rc;
     } else {
         c->cur = 0;
     }
-    // (keys_stale: see sort_direct, gkm_capi.hip)
-    sort_finished(c, ks, k, ks.canonical != 0, /*keys_stale*/ n > 0 && !c->msd_keys_final, /*keys_are_ranks*/ false);
+    // (keys_stale: what the sort just called reported, as in sort_direct, gkm_capi.hip; no k-mers, no keys)
+    sort_finished(c, ks, k, ks.canonical != 0, /*keys_stale*/ n > 0 && !keys_final, /*keys_are_ranks*/ false);
     return GK_OK;
 }

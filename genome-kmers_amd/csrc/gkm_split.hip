@@ -13,7 +13,6 @@
 // (kmers.py:1710-1711).  Canonical k-mers (gkm_canon.h) keep their class under reverse
 // complement, so the split applies to them unchanged.
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "gkm_canon.h"
@@ -599,6 +598,32 @@ static uint32_t homo_prefix(uint32_t ch, int pns) {
     return v;
 }
 
+static const char *const kTileTables[4] = {"split_cnt_r", "split_cnt_h", "split_off_r", "split_off_h"};
+// The class-B starts in [lo, hi) (lo a multiple of 32), of a key-range shard (rg) those whose prefix lies
+// in its interval: counts per tile, their scans, the stores.  *rest ("split_b_st0", *nR + 64) and *homo
+// ("split_h_st", *nH + 64): in start order.  The tile tables "split_cnt_r/_h", "split_off_r/_h": dead on return.
+static int class_b_select(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, const SplitRange *rg,
+                          uint32_t **rest, uint64_t *nR, uint32_t **homo, uint64_t *nH) {
+    const int pns = rg ? rg->pns : 4;
+    const uint32_t p4_lo = rg ? rg->p4_lo : 0u, p4_hi = rg ? rg->p4_hi : (1u << (4 * pns));
+    const unsigned ftiles = (unsigned)((hi - lo + kFlagTile - 1) / kFlagTile);
+    uint32_t *t[4];  // per tile: the counts of the rest and of the homopolymers, then their offsets
+    for (int i = 0; i < 4; ++i) GK_TRY_HIP(c, scratch(c, kTileTables[i], ftiles + 1, &t[i]));
+    int slot;
+    timer_begin(c, "split_b_select", &slot);
+    hipLaunchKernelGGL(class_b_select_kernel<false>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, lo, hi, ks.symbols,
+                       ks.canonical, p4_lo, p4_hi, pns, t[0], t[1], nullptr, nullptr, nullptr, nullptr);
+    GK_TRY_HIP(c, hipGetLastError());
+    GK_TRY_HIP(c, scan_u32_exclusive_pair(c, t[0], t[2], t[1], t[3], ftiles, nR, nH));
+    GK_TRY_HIP(c, scratch(c, "split_b_st0", *nR + 64, rest));
+    GK_TRY_HIP(c, scratch(c, "split_h_st", *nH + 64, homo));
+    hipLaunchKernelGGL(class_b_select_kernel<true>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, lo, hi, ks.symbols,
+                       ks.canonical, p4_lo, p4_hi, pns, t[0], t[1], t[2], t[3], *rest, *homo);
+    GK_TRY_HIP(c, hipGetLastError());
+    timer_end(c, slot);
+    return GK_OK;
+}
+
 // Class-B k-mers starting in [lo, hi) for key-range shards (gk_shard_class_b): the non-homopolymer
 // starts and the homopolymer runs (first start, count, canonical letter) to the host, in start
 // order, and their ownership bins added to hist (bins[d] = the pns-symbol prefix of digit d's
@@ -613,26 +638,9 @@ int split_shard_class_b(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
     if (lo % 32) return fail(c, GK_E_ARG, "shard lo must be a multiple of 32");
     GK_TRY_HIP(c, split_tables());
     const int k = ks.symbols;
-    const unsigned ftiles = (unsigned)((hi - lo + kFlagTile - 1) / kFlagTile);
-    uint32_t *cr, *chh, *orr, *ohh, *rs, *hs;
-    GK_TRY_HIP(c, scratch(c, "split_cnt_r", ftiles + 1, &cr));
-    GK_TRY_HIP(c, scratch(c, "split_cnt_h", ftiles + 1, &chh));
-    GK_TRY_HIP(c, scratch(c, "split_off_r", ftiles + 1, &orr));
-    GK_TRY_HIP(c, scratch(c, "split_off_h", ftiles + 1, &ohh));
-    int slot;
-    timer_begin(c, "split_b_select", &slot);
-    const uint32_t all = 1u << (4 * 4);
-    hipLaunchKernelGGL(class_b_select_kernel<false>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, lo, hi, k,
-                       ks.canonical, 0u, all, 4, cr, chh, nullptr, nullptr, nullptr, nullptr);
-    GK_TRY_HIP(c, hipGetLastError());
+    uint32_t *rs, *hs;
     uint64_t nR = 0, nH = 0;
-    GK_TRY_HIP(c, scan_u32_exclusive_pair(c, cr, orr, chh, ohh, ftiles, &nR, &nH));
-    GK_TRY_HIP(c, scratch(c, "split_b_st0", nR + 64, &rs));
-    GK_TRY_HIP(c, scratch(c, "split_h_st", nH + 64, &hs));
-    hipLaunchKernelGGL(class_b_select_kernel<true>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, lo, hi, k,
-                       ks.canonical, 0u, all, 4, cr, chh, orr, ohh, rs, hs);
-    GK_TRY_HIP(c, hipGetLastError());
-    timer_end(c, slot);
+    if (int rc = class_b_select(c, ks, lo, hi, nullptr, &rs, &nR, &hs, &nH)) return rc;
     const uint32_t nbins = (uint32_t)bins.size();
     if (nR > 0) {
         rest->resize(nR);
@@ -680,365 +688,333 @@ int split_shard_class_b(gk_ctx *c, const KeySpec &ks, uint64_t lo, uint64_t hi, 
 // ---------------------------------------------------------------------------------------------
 // driver
 // ---------------------------------------------------------------------------------------------
-int split_sort(gk_ctx *c, const KeySpec &ks, bool *used, const SplitRange *rg) {
-    *used = false;
-    const uint64_t L = c->sba_len;
-    const uint64_t n = rg ? L : c->n;  // key-range shards: the k-mer count is not known yet (<= L)
-    const int k = ks.symbols;
-    if (k > 64 || ks.bits != 4 || ks.lenbits || ks.symbols != ks.min_len) return GK_OK;
-    if (rg && k < rg->pns) return fail(c, GK_E_ARG, "split: key-range shards need k >= the prefix length");
-    GK_TRY_HIP(c, split_tables());
-    c->split_keys_final = false;
-    // final keys: the sorted order leaves with its W-word 4-bit keys -- B's from their own sort, A's
-    // written by the merge: expanded from the one-word 2-bit MSD keys (k <= 32), or read from a
-    // 2-bit packed copy of the sequence (k <= 63, round 5; GKM_NO_MERGE_KEYS=1: the re-encode after
-    // the sort instead) -- and needs no re-encode
-    const bool a_packed = k > 32 && k <= 63 && !opt("GKM_NO_MERGE_KEYS");
-    const int WK = k <= 32 || a_packed ? ks.words : 0;
+// What split_sort's stages hand on.  Scratch by stage ("dead": no later stage reads it):
+//   select    "split_b_st0" (b_st[0]), "split_h_st" (h_st): read until the splice.  From given lists also
+//             "split_g_rest", "split_own_rs/_ro" and, for the keep flags and their indices, "split_h_lf" /
+//             "split_h_idx": dead when the select returns, so the splice takes these two names again
+//   B sort    "split_b_st1", "split_b_st0g" (b_st[0] regrown to nB), "split_b_heads", "split_b_k0/_k1": its result
+//   splice    "split_h_cnt", "split_h_lf" / "split_h_idx" (letter flags), "split_h_grp", "split_h_first/_pos":
+//             dead at its end; "split_b_heads2" and "split_b_kf" are b_heads and b_keys from then on
+//   A sort    "split_a_keys": a_keys, where growing the key buffers would lose them
+//   finishes  "split_heads" (becomes c->heads); the merge alone: "split_g_first", "split_pos", "split_pk"
+struct SplitState {
+    int k = 0, WK = 0;      // symbols; key words the sort leaves final (0: re-encoded later, ensure_keys)
+    bool a_packed = false;  // the merge reads A's keys from the 2-bit packed sequence (32 < k <= 63)
+    uint64_t n = 0;         // k-mers of the enumeration; key-range shards: their bound, the sba's length
+    uint64_t nR = 0, nH = 0, nB = 0, nA = 0;  // B apart from homopolymers, B homopolymers, both; A
+    uint32_t *b_st[2] = {nullptr, nullptr}, *h_st = nullptr;  // B starts; the homopolymers', start order
+    int bres = 0;                                             // b_st[bres]: the B order, once sorted
+    uint8_t *b_heads = nullptr;        // group heads of the B order
+    const uint64_t *b_keys = nullptr;  // its 4-bit keys, word-major: stride nR, after the splice nB
+    const uint64_t *a_keys = nullptr;  // A's one-word 2-bit keys in sorted order (WK > 0, k <= 32)
+};
+
+// 1'. the B k-mers of every rank's position share, gathered (gk_shard_class_b): keep the
+// non-homopolymer ones whose prefix is in the rank's interval, expand the owned runs
+static int select_given(gk_ctx *c, const KeySpec &ks, const SplitRange &rg, SplitState *s) {
+    uint32_t *g_rest = nullptr, *keep = nullptr, *none;  // (none: the scan's tile tables, sized as ever, not read here)
+    for (const char *t : kTileTables) GK_TRY_HIP(c, scratch(c, t, (c->sba_len + kFlagTile - 1) / kFlagTile + 1, &none));
     int slot;
-    // 1. class B starts: homopolymers (one letter k times) apart from the rest
-    uint32_t *b_st[2], *h_st;
-    const unsigned ftiles = (unsigned)((L + kFlagTile - 1) / kFlagTile);
-    uint32_t *cr, *chh, *orr, *ohh;
-    GK_TRY_HIP(c, scratch(c, "split_cnt_r", ftiles + 1, &cr));
-    GK_TRY_HIP(c, scratch(c, "split_cnt_h", ftiles + 1, &chh));
-    GK_TRY_HIP(c, scratch(c, "split_off_r", ftiles + 1, &orr));
-    GK_TRY_HIP(c, scratch(c, "split_off_h", ftiles + 1, &ohh));
-    const int pns = rg ? rg->pns : 4;
-    const uint32_t p4_lo = rg ? rg->p4_lo : 0u, p4_hi = rg ? rg->p4_hi : (1u << (4 * pns));
-    uint64_t nR = 0, nH = 0;
-    if (rg && rg->given) {
-        // 1'. the B k-mers of every rank's position share, gathered (gk_shard_class_b): keep the
-        // non-homopolymer ones whose prefix is in the rank's interval, expand the owned runs
-        timer_begin(c, "split_b_given", &slot);
-        uint32_t *g_rest = nullptr;
+    timer_begin(c, "split_b_given", &slot);
+    if (rg.n_rest > 0) {
         uint8_t *f;
-        if (rg->n_rest > 0) {
-            GK_TRY_HIP(c, scratch(c, "split_g_rest", rg->n_rest + 64, &g_rest));
-            GK_TRY_HIP(c, scratch(c, "split_h_lf", rg->n_rest + 64, &f));
-            GK_TRY_HIP(c, scratch(c, "split_h_idx", rg->n_rest + 64, &b_st[1]));
-            GK_TRY_HIP(c, hipMemcpyAsync(g_rest, rg->rest, 4 * rg->n_rest, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(b_keep_kernel, dim3(grid_of_n(rg->n_rest)), dim3(256), 0, c->stream, c->sba, g_rest,
-                               rg->n_rest, k, ks.canonical, pns, p4_lo, p4_hi, f);
-            GK_TRY_HIP(c, hipGetLastError());
-            GK_TRY_HIP(c, select_flags(c, f, rg->n_rest, b_st[1], &nR));
-        }
-        std::vector<uint32_t> own_s;
-        std::vector<uint64_t> own_o;
-        for (uint64_t g = 0; g < rg->n_runs; ++g) {
-            const uint32_t x = homo_prefix(rg->runs[3 * g + 2], pns);
-            if (x < p4_lo || x >= p4_hi) continue;
-            own_s.push_back(rg->runs[3 * g]);
-            own_o.push_back(nH);
-            nH += rg->runs[3 * g + 1];
-        }
-        GK_TRY_HIP(c, scratch(c, "split_b_st0", nR + 64, &b_st[0]));
-        GK_TRY_HIP(c, scratch(c, "split_h_st", nH + 64, &h_st));
-        if (nR > 0) {
-            hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_of_n(nR)), dim3(256), 0, c->stream, g_rest, b_st[1], nR,
-                               b_st[0]);
-            GK_TRY_HIP(c, hipGetLastError());
-        }
-        if (nH > 0) {
-            uint32_t *d_rs;
-            uint64_t *d_ro;
-            GK_TRY_HIP(c, scratch(c, "split_own_rs", own_s.size() + 1, &d_rs));
-            GK_TRY_HIP(c, scratch(c, "split_own_ro", own_o.size() + 1, &d_ro));
-            GK_TRY_HIP(c, hipMemcpyAsync(d_rs, own_s.data(), 4 * own_s.size(), hipMemcpyHostToDevice, c->stream));
-            GK_TRY_HIP(c, hipMemcpyAsync(d_ro, own_o.data(), 8 * own_o.size(), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(expand_runs_kernel, dim3(grid_of_n(nH)), dim3(256), 0, c->stream, d_rs, d_ro,
-                               (uint32_t)own_s.size(), nH, h_st);
-            GK_TRY_HIP(c, hipGetLastError());
-            GK_TRY_HIP(c, hipStreamSynchronize(c->stream));  // own_s / own_o leave scope
-        }
-        timer_end(c, slot);
-    } else {
-    timer_begin(c, "split_b_select", &slot);
-    hipLaunchKernelGGL(class_b_select_kernel<false>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, 0ull, L, k,
-                       ks.canonical, p4_lo, p4_hi, pns, cr, chh, nullptr, nullptr, nullptr, nullptr);
-    GK_TRY_HIP(c, hipGetLastError());
-    GK_TRY_HIP(c, scan_u32_exclusive_pair(c, cr, orr, chh, ohh, ftiles, &nR, &nH));
-    GK_TRY_HIP(c, scratch(c, "split_b_st0", nR + 64, &b_st[0]));
-    GK_TRY_HIP(c, scratch(c, "split_h_st", nH + 64, &h_st));
-    hipLaunchKernelGGL(class_b_select_kernel<true>, dim3(ftiles), dim3(256), 0, c->stream, c->sba, 0ull, L, k,
-                       ks.canonical, p4_lo, p4_hi, pns, cr, chh, orr, ohh, b_st[0], h_st);
-    GK_TRY_HIP(c, hipGetLastError());
+        GK_TRY_HIP(c, scratch(c, "split_g_rest", rg.n_rest + 64, &g_rest));
+        GK_TRY_HIP(c, scratch(c, "split_h_lf", rg.n_rest + 64, &f));
+        GK_TRY_HIP(c, scratch(c, "split_h_idx", rg.n_rest + 64, &keep));
+        GK_TRY_HIP(c, hipMemcpyAsync(g_rest, rg.rest, 4 * rg.n_rest, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(b_keep_kernel, dim3(grid_of_n(rg.n_rest)), dim3(256), 0, c->stream, c->sba, g_rest,
+                           rg.n_rest, s->k, ks.canonical, rg.pns, rg.p4_lo, rg.p4_hi, f);
+        GK_TRY_HIP(c, hipGetLastError());
+        GK_TRY_HIP(c, select_flags(c, f, rg.n_rest, keep, &s->nR));
+    }
+    std::vector<uint32_t> own_s;
+    std::vector<uint64_t> own_o;
+    for (uint64_t g = 0; g < rg.n_runs; ++g) {
+        const uint32_t x = homo_prefix(rg.runs[3 * g + 2], rg.pns);
+        if (x < rg.p4_lo || x >= rg.p4_hi) continue;
+        own_s.push_back(rg.runs[3 * g]);
+        own_o.push_back(s->nH);
+        s->nH += rg.runs[3 * g + 1];
+    }
+    GK_TRY_HIP(c, scratch(c, "split_b_st0", s->nR + 64, &s->b_st[0]));
+    GK_TRY_HIP(c, scratch(c, "split_h_st", s->nH + 64, &s->h_st));
+    if (s->nR > 0) {
+        hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_of_n(s->nR)), dim3(256), 0, c->stream, g_rest, keep, s->nR,
+                           s->b_st[0]);
+        GK_TRY_HIP(c, hipGetLastError());
+    }
+    if (s->nH > 0) {
+        uint32_t *d_rs;
+        uint64_t *d_ro;
+        GK_TRY_HIP(c, scratch(c, "split_own_rs", own_s.size() + 1, &d_rs));
+        GK_TRY_HIP(c, scratch(c, "split_own_ro", own_o.size() + 1, &d_ro));
+        GK_TRY_HIP(c, hipMemcpyAsync(d_rs, own_s.data(), 4 * own_s.size(), hipMemcpyHostToDevice, c->stream));
+        GK_TRY_HIP(c, hipMemcpyAsync(d_ro, own_o.data(), 8 * own_o.size(), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(expand_runs_kernel, dim3(grid_of_n(s->nH)), dim3(256), 0, c->stream, d_rs, d_ro,
+                           (uint32_t)own_s.size(), s->nH, s->h_st);
+        GK_TRY_HIP(c, hipGetLastError());
+        GK_TRY_HIP(c, hipStreamSynchronize(c->stream));  // own_s / own_o leave scope
+    }
     timer_end(c, slot);
-    }
-    const uint64_t nB = nR + nH;
-    if (nB > n) return fail(c, GK_E_HIP, "split: more class-B k-mers than k-mers");
-    if (!rg && nB * 4 > n) return GK_OK;  // mostly non-ACGT k-mers: the plain 4-bit MSD is the better sort
-    *used = true;
-    uint64_t nA = rg ? 0 : n - nB;
+    return GK_OK;
+}
 
-    // 2. sort the non-homopolymer B k-mers: 4-bit keys, LSD (on a swapped-in context of nR elements)
-    uint64_t *b_k[2];
-    uint8_t *b_heads;
-    int bres = 0;
-    GK_TRY_HIP(c, scratch(c, "split_b_st1", nB + 64, &b_st[1]));
-    if (nH > 0 && nR + 64 < nB + 64) {  // b_st[0] also receives the assembled B order (bres flips)
+// 2. sort the non-homopolymer B k-mers: 4-bit keys, LSD, with the B buffers as the context's operands
+static int sort_b_rest(gk_ctx *c, const KeySpec &ks, bool ranged, SplitState *s) {
+    GK_TRY_HIP(c, scratch(c, "split_b_st1", s->nB + 64, &s->b_st[1]));
+    if (s->nH > 0 && s->nR + 64 < s->nB + 64) {  // b_st[0] also receives the assembled B order (bres flips)
         uint32_t *grown;
-        GK_TRY_HIP(c, scratch(c, "split_b_st0g", nB + 64, &grown));
-        GK_TRY_HIP(c, hipMemcpyAsync(grown, b_st[0], 4 * nR, hipMemcpyDeviceToDevice, c->stream));
-        b_st[0] = grown;
+        GK_TRY_HIP(c, scratch(c, "split_b_st0g", s->nB + 64, &grown));
+        GK_TRY_HIP(c, hipMemcpyAsync(grown, s->b_st[0], 4 * s->nR, hipMemcpyDeviceToDevice, c->stream));
+        s->b_st[0] = grown;
     }
-    GK_TRY_HIP(c, scratch(c, "split_b_heads", nB + 64, &b_heads));
-    if (nR > 0) {
-        const int W = ks.words;
-        if (rg) {  // key-range shards: nothing sized the radix state for this context yet
-            const uint64_t sv_n = c->n;
-            c->n = 0;  // (no start array to keep)
-            const int re = ensure_elems(c, std::max<uint64_t>(c->elem_cap, nR + 1), 1);
-            c->n = sv_n;
-            if (re != GK_OK) return re;
-        }
-        GK_TRY_HIP(c, scratch(c, "split_b_k0", W * (nR + 64), &b_k[0]));
-        GK_TRY_HIP(c, scratch(c, "split_b_k1", W * (nR + 64), &b_k[1]));
-        const uint64_t sv_n = c->n;
-        uint64_t *sv_k[2] = {c->keys[0], c->keys[1]};
-        uint32_t *sv_v[2] = {c->vals[0], c->vals[1]};
-        const int sv_cur = c->cur;
-        c->n = nR;
-        c->keys[0] = b_k[0];
-        c->keys[1] = b_k[1];
-        c->vals[0] = b_st[0];
-        c->vals[1] = b_st[1];
-        c->cur = 0;
+    GK_TRY_HIP(c, scratch(c, "split_b_heads", s->nB + 64, &s->b_heads));
+    if (s->nR == 0) return GK_OK;
+    const int W = ks.words;
+    if (ranged) {  // key-range shards: nothing sized the radix state for this context yet
+        ScopedOperands none(c, 0);  // (no start array to keep)
+        if (int rc = ensure_elems(c, std::max<uint64_t>(c->elem_cap, s->nR + 1), 1)) return rc;
+    }
+    uint64_t *b_k[2];
+    GK_TRY_HIP(c, scratch(c, "split_b_k0", W * (s->nR + 64), &b_k[0]));
+    GK_TRY_HIP(c, scratch(c, "split_b_k1", W * (s->nR + 64), &b_k[1]));
+    {
+        ScopedOperands b(c, s->nR, b_k, s->b_st, 0);
+        int slot;
         timer_begin(c, "split_b_encode", &slot);
-        hipError_t e = launch_encode_gather(c, ks, b_st[0], nR, b_k[0]);
+        const hipError_t e = launch_encode_gather(c, ks, s->b_st[0], s->nR, b_k[0]);
         timer_end(c, slot);
-        int rc = e == hipSuccess ? radix_sort(c, W, ks.total_bits, false) : GK_E_HIP;
-        bres = c->cur;
-        c->n = sv_n;
-        c->keys[0] = sv_k[0];
-        c->keys[1] = sv_k[1];
-        c->vals[0] = sv_v[0];
-        c->vals[1] = sv_v[1];
-        c->cur = sv_cur;
         if (e != hipSuccess) return hip_fail(c, e, "split: encode B");
-        if (rc != GK_OK) return rc;
-        hipLaunchKernelGGL(key_heads_kernel, dim3(grid_of_n(nR)), dim3(256), 0, c->stream, b_k[bres], nR, W, b_heads);
-        GK_TRY_HIP(c, hipGetLastError());
+        if (int rc = radix_sort(c, W, ks.total_bits, false)) return rc;
+        s->bres = c->cur;  // (of the B pair: read before the guard goes)
     }
-    // B's final keys (word-major, stride nB): the rest's sorted keys, with the homopolymer groups'
-    // constant keys spliced in below
-    const uint64_t *b_keys = nR > 0 ? b_k[bres] : nullptr;
+    s->b_keys = b_k[s->bres];
+    hipLaunchKernelGGL(key_heads_kernel, dim3(grid_of_n(s->nR)), dim3(256), 0, c->stream, s->b_keys, s->nR, W,
+                       s->b_heads);
+    GK_TRY_HIP(c, hipGetLastError());
+    return GK_OK;
+}
+
+// 2b. the homopolymer groups (one per (canonical) letter, members in start order) go into the sorted B run
+// at their insertion points: at most 15 segment copies; their constant keys into the rest's sorted keys
+static int splice_homopolymers(gk_ctx *c, const KeySpec &ks, SplitState *s) {
+    const uint64_t nR = s->nR, nH = s->nH, nB = s->nB;
+    const int WK = s->WK;
     uint64_t *bkf = nullptr;
-    if (WK && nH > 0) GK_TRY_HIP(c, scratch(c, "split_b_kf", (uint64_t)WK * (nB + 64), &bkf));
-    if (nH > 0) {
-        // 2b. the homopolymer groups (one per (canonical) letter, members in start order) go into
-        // the sorted B run at their insertion points: at most 15 segment copies
-        timer_begin(c, "split_b_homo", &slot);
-        uint32_t *cnt;
-        GK_TRY_HIP(c, scratch(c, "split_h_cnt", 256, &cnt));
-        GK_TRY_HIP(c, hipMemsetAsync(cnt, 0, 4 * 256, c->stream));
-        hipLaunchKernelGGL(homo_count_kernel, dim3(grid_of_n(nH)), dim3(256), 0, c->stream, c->sba, h_st, nH,
-                           ks.canonical, cnt);
+    if (WK) GK_TRY_HIP(c, scratch(c, "split_b_kf", (uint64_t)WK * (nB + 64), &bkf));
+    int slot;
+    timer_begin(c, "split_b_homo", &slot);
+    uint32_t *cnt;
+    GK_TRY_HIP(c, scratch(c, "split_h_cnt", 256, &cnt));
+    GK_TRY_HIP(c, hipMemsetAsync(cnt, 0, 4 * 256, c->stream));
+    hipLaunchKernelGGL(homo_count_kernel, dim3(grid_of_n(nH)), dim3(256), 0, c->stream, c->sba, s->h_st, nH,
+                       ks.canonical, cnt);
+    GK_TRY_HIP(c, hipGetLastError());
+    std::vector<uint32_t> hc(256);
+    GK_TRY_HIP(c, hipMemcpyAsync(hc.data(), cnt, 4 * 256, hipMemcpyDeviceToHost, c->stream));
+    GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> letters;  // ascending byte = ascending key of letter^k
+    for (int ch = 0; ch < 256; ++ch)
+        if (hc[ch]) letters.push_back((uint32_t)ch);
+    // groups by letter, in letter order, into grp (stable: h_st is in start order)
+    uint32_t *grp = s->h_st, *tmp_idx, *grp2;
+    if (letters.size() > 1) {
+        uint8_t *lf;
+        GK_TRY_HIP(c, scratch(c, "split_h_lf", nH + 64, &lf));
+        GK_TRY_HIP(c, scratch(c, "split_h_idx", nH + 64, &tmp_idx));
+        GK_TRY_HIP(c, scratch(c, "split_h_grp", nH + 64, &grp2));
+        uint64_t at = 0;
+        for (uint32_t ch : letters) {
+            hipLaunchKernelGGL(homo_flags_kernel, dim3(grid_of_n(nH)), dim3(256), 0, c->stream, c->sba, s->h_st, nH,
+                               ks.canonical, ch, lf);
+            uint64_t m = 0;
+            GK_TRY_HIP(c, select_flags(c, lf, nH, tmp_idx, &m));
+            hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_of_n(m)), dim3(256), 0, c->stream, s->h_st, tmp_idx, m,
+                               grp2 + at);
+            GK_TRY_HIP(c, hipGetLastError());
+            at += m;
+        }
+        grp = grp2;
+    }
+    // insertion points: the number of sorted non-homopolymer B k-mers below each group's k-mer
+    std::vector<uint32_t> ins(letters.size(), 0), first(letters.size(), 0);  // first: each group's offset in grp
+    for (size_t g = 1; g < letters.size(); ++g) first[g] = first[g - 1] + hc[letters[g - 1]];
+    const uint32_t *rst = s->b_st[s->bres];
+    if (nR > 0) {
+        uint32_t *d_first, *d_pos;
+        GK_TRY_HIP(c, scratch(c, "split_h_first", letters.size() + 1, &d_first));
+        GK_TRY_HIP(c, scratch(c, "split_h_pos", letters.size() + 1, &d_pos));
+        GK_TRY_HIP(c, hipMemcpyAsync(d_first, first.data(), 4 * letters.size(), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(b_group_pos_kernel, dim3(1), dim3(256), 0, c->stream, c->sba, s->k, ks.canonical, rst, nR,
+                           grp, d_first, (uint64_t)letters.size(), d_pos);
         GK_TRY_HIP(c, hipGetLastError());
-        std::vector<uint32_t> hc(256);
-        GK_TRY_HIP(c, hipMemcpyAsync(hc.data(), cnt, 4 * 256, hipMemcpyDeviceToHost, c->stream));
+        GK_TRY_HIP(c, hipMemcpyAsync(ins.data(), d_pos, 4 * letters.size(), hipMemcpyDeviceToHost, c->stream));
         GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        std::vector<uint32_t> letters;  // ascending byte = ascending key of letter^k
-        for (int ch = 0; ch < 256; ++ch)
-            if (hc[ch]) letters.push_back((uint32_t)ch);
-        // groups by letter, in letter order, into grp (stable: h_st is in start order)
-        uint32_t *grp = h_st, *tmp_idx, *grp2;
-        if (letters.size() > 1) {
-            uint8_t *lf;
-            GK_TRY_HIP(c, scratch(c, "split_h_lf", nH + 64, &lf));
-            GK_TRY_HIP(c, scratch(c, "split_h_idx", nH + 64, &tmp_idx));
-            GK_TRY_HIP(c, scratch(c, "split_h_grp", nH + 64, &grp2));
-            uint64_t at = 0;
-            for (uint32_t ch : letters) {
-                hipLaunchKernelGGL(homo_flags_kernel, dim3(grid_of_n(nH)), dim3(256), 0, c->stream, c->sba, h_st, nH,
-                                   ks.canonical, ch, lf);
-                uint64_t m = 0;
-                GK_TRY_HIP(c, select_flags(c, lf, nH, tmp_idx, &m));
-                hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_of_n(m)), dim3(256), 0, c->stream, h_st, tmp_idx, m,
-                                   grp2 + at);
-                GK_TRY_HIP(c, hipGetLastError());
-                at += m;
-            }
-            grp = grp2;
-        }
-        // insertion points: the number of sorted non-homopolymer B k-mers below each group's k-mer
-        std::vector<uint32_t> ins(letters.size(), 0), first(letters.size());
-        {
-            uint64_t at = 0;
-            for (size_t g = 0; g < letters.size(); ++g) {
-                first[g] = (uint32_t)at;
-                at += hc[letters[g]];
-            }
-        }
-        if (nR > 0) {
-            uint32_t *d_first, *d_pos;
-            GK_TRY_HIP(c, scratch(c, "split_h_first", letters.size() + 1, &d_first));
-            GK_TRY_HIP(c, scratch(c, "split_h_pos", letters.size() + 1, &d_pos));
-            GK_TRY_HIP(c, hipMemcpyAsync(d_first, first.data(), 4 * letters.size(), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(b_group_pos_kernel, dim3(1), dim3(256), 0, c->stream, c->sba, k, ks.canonical,
-                               b_st[bres], nR, grp, d_first, (uint64_t)letters.size(), d_pos);
-            GK_TRY_HIP(c, hipGetLastError());
-            GK_TRY_HIP(c, hipMemcpyAsync(ins.data(), d_pos, 4 * letters.size(), hipMemcpyDeviceToHost, c->stream));
-            GK_TRY_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        // assemble the B order into the other start buffer (+ heads into a fresh array)
-        uint32_t *fst = b_st[bres ^ 1];
-        uint8_t *fhd;
-        GK_TRY_HIP(c, scratch(c, "split_b_heads2", nB + 64, &fhd));
-        uint64_t rcur = 0, out = 0;
-        auto copy_rest = [&](uint64_t upto) -> hipError_t {
-            const uint64_t m = upto - rcur;
-            if (!m) return hipSuccess;
-            hipError_t e = hipMemcpyAsync(fst + out, b_st[bres] + rcur, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(fhd + out, b_heads + rcur, m, hipMemcpyDeviceToDevice, c->stream);
-            for (int q = 0; q < WK && e == hipSuccess; ++q)
-                e = hipMemcpyAsync(bkf + (uint64_t)q * nB + out, b_keys + (uint64_t)q * nR + rcur, 8 * m,
-                                   hipMemcpyDeviceToDevice, c->stream);
-            rcur = upto;
-            out += m;
-            return e;
-        };
-        for (size_t g = 0; g < letters.size(); ++g) {
-            GK_TRY_HIP(c, copy_rest(ins[g]));
-            const uint64_t m = hc[letters[g]];
-            GK_TRY_HIP(c, hipMemcpyAsync(fst + out, grp + first[g], 4 * m, hipMemcpyDeviceToDevice, c->stream));
-            GK_TRY_HIP(c, hipMemsetAsync(fhd + out, 0, m, c->stream));
-            GK_TRY_HIP(c, hipMemsetAsync(fhd + out, 1, 1, c->stream));  // one group: one head
-            if (WK) {  // the group's k-mer: its (canonical) letter k times
-                const uint64_t c4 = letter_code4(letters[g]);
-                for (int q = 0; q < WK; ++q) {  // q: word from the most significant end
-                    uint64_t v = 0;
-                    const int lo_sym = 16 * (WK - 1 - q);  // nibble index of the word's bit 0
-                    for (int j = lo_sym; j < std::min(lo_sym + 16, k); ++j) v |= c4 << (4 * (j - lo_sym));
-                    hipLaunchKernelGGL(fill_u64_kernel, dim3(grid_of_n(m)), dim3(256), 0, c->stream,
-                                       bkf + (uint64_t)q * nB + out, m, v);
-                }
-                GK_TRY_HIP(c, hipGetLastError());
-            }
-            out += m;
-        }
-        GK_TRY_HIP(c, copy_rest(nR));
-        b_heads = fhd;
-        bres ^= 1;
-        b_keys = bkf;
-        timer_end(c, slot);
     }
+    // assemble the B order into the other start buffer (+ heads into a fresh array)
+    uint32_t *fst = s->b_st[s->bres ^ 1];
+    uint8_t *fhd;
+    GK_TRY_HIP(c, scratch(c, "split_b_heads2", nB + 64, &fhd));
+    uint64_t rcur = 0, out = 0;
+    auto copy_rest = [&](uint64_t upto) -> hipError_t {
+        const uint64_t m = upto - rcur;
+        if (!m) return hipSuccess;
+        hipError_t e = hipMemcpyAsync(fst + out, rst + rcur, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(fhd + out, s->b_heads + rcur, m, hipMemcpyDeviceToDevice, c->stream);
+        for (int q = 0; q < WK && e == hipSuccess; ++q)
+            e = hipMemcpyAsync(bkf + (uint64_t)q * nB + out, s->b_keys + (uint64_t)q * nR + rcur, 8 * m,
+                               hipMemcpyDeviceToDevice, c->stream);
+        rcur = upto;
+        out += m;
+        return e;
+    };
+    for (size_t g = 0; g < letters.size(); ++g) {
+        GK_TRY_HIP(c, copy_rest(ins[g]));
+        const uint64_t m = hc[letters[g]];
+        GK_TRY_HIP(c, hipMemcpyAsync(fst + out, grp + first[g], 4 * m, hipMemcpyDeviceToDevice, c->stream));
+        GK_TRY_HIP(c, hipMemsetAsync(fhd + out, 0, m, c->stream));
+        GK_TRY_HIP(c, hipMemsetAsync(fhd + out, 1, 1, c->stream));  // one group: one head
+        if (WK) {  // the group's k-mer: its (canonical) letter k times
+            const uint64_t c4 = letter_code4(letters[g]);
+            for (int q = 0; q < WK; ++q) {  // q: word from the most significant end
+                uint64_t v = 0;
+                const int lo_sym = 16 * (WK - 1 - q);  // nibble index of the word's bit 0
+                for (int j = lo_sym; j < std::min(lo_sym + 16, s->k); ++j) v |= c4 << (4 * (j - lo_sym));
+                hipLaunchKernelGGL(fill_u64_kernel, dim3(grid_of_n(m)), dim3(256), 0, c->stream,
+                                   bkf + (uint64_t)q * nB + out, m, v);
+            }
+            GK_TRY_HIP(c, hipGetLastError());
+        }
+        out += m;
+    }
+    GK_TRY_HIP(c, copy_rest(nR));
+    s->b_heads = fhd;
+    s->bres ^= 1;
+    s->b_keys = bkf;
+    timer_end(c, slot);
+    return GK_OK;
+}
 
-    // 3. sort A: the 2-bit MSD over the ACGT-only k-mers (its count is checked against nA)
-    KeySpec ka = ks;
-    ka.bits = 2;
-    ka.total_bits = 2 * k;
-    ka.words = (ka.total_bits + 63) / 64;
-    ka.acgt_only = 1;
-    int rc;
-    const uint64_t *a_keys = nullptr;  // A's final 2-bit keys (WK, k <= 32)
-    c->msd_force_keys = WK > 0 && !a_packed;
-    if (rg) {  // the rank's ACGT-only k-mers: select + MSD (gkm_msd.hip); room for the merge after
-        rc = msd_sort_range(c, ka, rg->d_lo, rg->d_hi, &nA);
-        c->msd_force_keys = false;
-        if (rc != GK_OK) return rc;
+// 3. sort A, the 2-bit MSD over the ACGT-only k-mers, into vals[0] / keys[0] with c->heads: a key-range
+// shard's (select + MSD, which finds nA), else all nA (checked) from a prefetched L0 (gk_sort_hint) or none
+static int sort_a(gk_ctx *c, const KeySpec &ks, const SplitRange *rg, SplitState *s) {
+    const KeySpec ka = acgt_spec(ks);
+    const int WK = s->WK;
+    const bool want_keys = WK > 0 && !s->a_packed;  // A's final 2-bit keys (k <= 32): the merge expands them
+    if (rg) {  // room for the merge after
+        if (int rc = msd_sort_range(c, ka, rg->d_lo, rg->d_hi, want_keys, &s->nA, nullptr)) return rc;
         c->have_starts = true;
-        a_keys = a_packed ? nullptr : c->keys[0];
-        if (WK && !a_packed && nA + nB + 1 > c->elem_cap) {  // growing the buffers below does not keep the keys
+        s->a_keys = s->a_packed ? nullptr : c->keys[0];
+        if (want_keys && s->nA + s->nB + 1 > c->elem_cap) {  // growing the buffers below does not keep the keys
             uint64_t *ak;
-            GK_TRY_HIP(c, scratch(c, "split_a_keys", nA + 64, &ak));
-            GK_TRY_HIP(c, hipMemcpyAsync(ak, c->keys[0], 8 * nA, hipMemcpyDeviceToDevice, c->stream));
-            a_keys = ak;
+            GK_TRY_HIP(c, scratch(c, "split_a_keys", s->nA + 64, &ak));
+            GK_TRY_HIP(c, hipMemcpyAsync(ak, c->keys[0], 8 * s->nA, hipMemcpyDeviceToDevice, c->stream));
+            s->a_keys = ak;
         }
-        rc = ensure_elems(c, nA + nB + 1, 1);  // keeps vals[0] (nA)
-        if (rc != GK_OK) return rc;
+        if (int rc = ensure_elems(c, s->nA + s->nB + 1, 1)) return rc;  // keeps vals[0] (nA)
         // the merge's output buffer at its final width now, not mid-merge (keys[0] may hold A's
-        // keys: it is only regrown on the nA == 0 path below, where they are not used)
-        if (WK && a_keys != c->keys[1])
+        // keys: it is only regrown by finish_only_b, where they are not used)
+        if (WK && s->a_keys != c->keys[1])
             if (int r = grow_key_buffer(c, 1, WK)) return r;
-        c->n = nA + nB;
-    } else {
-        // both key buffers at the final key width before the A sort (which uses word 0 of each):
-        // nothing is freed or re-allocated between the A sort and the merge -- except with a
-        // prefetched class-A L0 (gk_sort_hint) in keys[1] / vals[1]: keys[1] grows after the A sort,
-        // whose result is in buffer 0 (keys[1] is its scratch by then)
-        c->n = nA;
-        const bool pre = nA > 0 && prefetch_matches(c, ka);
-        c->n = n;
-        if (WK) {
-            if (!a_packed)
-                if (int r = grow_key_buffer(c, 0, WK)) return r;
-            if (!pre)
-                if (int r = grow_key_buffer(c, 1, WK)) return r;
-        }
-        c->n = nA;
-        rc = nA > 0 ? (pre ? msd_sort_prefetched(c, ka) : msd_sort(c, ka)) : GK_OK;
-        c->msd_force_keys = false;
-        c->n = n;
-        if (rc != GK_OK) return rc;
-        if (pre && WK) {
-            if (c->cur != 0) return fail(c, GK_E_STATE, "split sort: the prefetched A sort did not end in buffer 0");
-            if (int r = grow_key_buffer(c, 1, WK)) return r;
-        }
-        a_keys = a_packed ? nullptr : c->keys[0];
-    }
-    if (nA == 0) {  // all B: the B order is the order
-        GK_TRY_HIP(c, hipMemcpyAsync(c->vals[0], b_st[bres], 4 * nB, hipMemcpyDeviceToDevice, c->stream));
-        uint8_t *hd;
-        GK_TRY_HIP(c, scratch(c, "split_heads", n + 64, &hd));
-        GK_TRY_HIP(c, hipMemcpyAsync(hd, b_heads, nB, hipMemcpyDeviceToDevice, c->stream));
-        if (WK) {  // (the B keys alone: A's packed-sequence path is not involved)
-            if (b_keys == c->keys[0]) return fail(c, GK_E_STATE, "split sort: B keys alias the key buffer");
-            if (int r = grow_key_buffer(c, 0, WK)) return r;
-            GK_TRY_HIP(c, hipMemcpyAsync(c->keys[0], b_keys, 8 * (uint64_t)WK * nB, hipMemcpyDeviceToDevice,
-                                         c->stream));  // stride nB == n
-            c->split_keys_final = true;
-        }
-        c->cur = 0;
-        c->heads = hd;
-        c->heads_valid = true;
+        c->n = s->nA + s->nB;  // the rank's k-mer count: split_sort's documented result for key-range shards
         return GK_OK;
     }
-    if (nB == 0) {  // msd_sort left vals[0] / heads in place; A's keys expanded next to them
-        if (WK && !a_packed) {  // (k > 32: the keys are re-encoded after the sort)
-            if (a_keys == c->keys[1]) return fail(c, GK_E_STATE, "split sort: A keys alias the output buffer");
-            if (int r = grow_key_buffer(c, 1, WK)) return r;
-            const uint64_t nn = nA;
-            if (WK == 1)
-                hipLaunchKernelGGL(expand_keys_kernel<1>, dim3(grid_of_n(nn)), dim3(256), 0, c->stream, a_keys, nn, k,
-                                   c->keys[1]);
-            else
-                hipLaunchKernelGGL(expand_keys_kernel<2>, dim3(grid_of_n(nn)), dim3(256), 0, c->stream, a_keys, nn, k,
-                                   c->keys[1]);
-            GK_TRY_HIP(c, hipGetLastError());
-            GK_TRY_HIP(c, hipMemcpyAsync(c->vals[1], c->vals[0], 4 * nn, hipMemcpyDeviceToDevice, c->stream));
-            c->cur = 1;
-            c->split_keys_final = true;
-        }
-        return GK_OK;
+    // both key buffers at the final key width before the A sort (which uses word 0 of each): nothing is freed
+    // or re-allocated between the A sort and the merge -- except with a prefetched class-A L0 in keys[1] /
+    // vals[1]: keys[1] grows after the A sort, whose result is in buffer 0 (keys[1] is its scratch by then)
+    const bool pre = s->nA > 0 && prefetch_matches(c, ka, s->nA);
+    if (WK && !s->a_packed)
+        if (int r = grow_key_buffer(c, 0, WK)) return r;
+    if (WK && !pre)
+        if (int r = grow_key_buffer(c, 1, WK)) return r;
+    if (s->nA > 0)
+        if (int rc = pre ? msd_sort_prefetched(c, ka, s->nA, want_keys, nullptr)
+                         : msd_sort(c, ka, s->nA, want_keys, nullptr))
+            return rc;
+    if (pre && WK) {
+        if (c->cur != 0) return fail(c, GK_E_STATE, "split sort: the prefetched A sort did not end in buffer 0");
+        if (int r = grow_key_buffer(c, 1, WK)) return r;
     }
+    s->a_keys = s->a_packed ? nullptr : c->keys[0];
+    return GK_OK;
+}
 
-    // 4. merge: B groups, their insertion points in A, the interleave into vals[1] + heads
+// the sort's outcome, recorded here alone: the order vals[cur], its group heads, whether keys[cur] is final
+static int split_done(gk_ctx *c, int cur, uint8_t *heads, bool keys, bool *keys_final) {
+    c->cur = cur;
+    c->heads = heads;
+    c->heads_valid = true;
+    *keys_final = keys;
+    return GK_OK;
+}
+
+// no A k-mer (as in a key-range shard's share): the B order is the order
+static int finish_only_b(gk_ctx *c, const SplitState &s, bool *keys_final) {
+    GK_TRY_HIP(c, hipMemcpyAsync(c->vals[0], s.b_st[s.bres], 4 * s.nB, hipMemcpyDeviceToDevice, c->stream));
+    uint8_t *hd;
+    GK_TRY_HIP(c, scratch(c, "split_heads", s.n + 64, &hd));
+    GK_TRY_HIP(c, hipMemcpyAsync(hd, s.b_heads, s.nB, hipMemcpyDeviceToDevice, c->stream));
+    if (s.WK) {  // (the B keys alone: A's packed-sequence path is not involved)
+        if (s.b_keys == c->keys[0]) return fail(c, GK_E_STATE, "split sort: B keys alias the key buffer");
+        if (int r = grow_key_buffer(c, 0, s.WK)) return r;
+        GK_TRY_HIP(c, hipMemcpyAsync(c->keys[0], s.b_keys, 8 * (uint64_t)s.WK * s.nB, hipMemcpyDeviceToDevice,
+                                     c->stream));  // stride nB == n
+    }
+    return split_done(c, 0, hd, s.WK > 0, keys_final);
+}
+
+// no B k-mer: the A sort left vals[0] and c->heads in place; A's keys are expanded next to them (k <= 32)
+static int finish_only_a(gk_ctx *c, const SplitState &s, bool *keys_final) {
+    const bool keys = s.WK && !s.a_packed;
+    if (keys) {
+        if (s.a_keys == c->keys[1]) return fail(c, GK_E_STATE, "split sort: A keys alias the output buffer");
+        if (int r = grow_key_buffer(c, 1, s.WK)) return r;
+        const dim3 g(grid_of_n(s.nA)), b(256);
+        if (s.WK == 1) hipLaunchKernelGGL(expand_keys_kernel<1>, g, b, 0, c->stream, s.a_keys, s.nA, s.k, c->keys[1]);
+        else hipLaunchKernelGGL(expand_keys_kernel<2>, g, b, 0, c->stream, s.a_keys, s.nA, s.k, c->keys[1]);
+        GK_TRY_HIP(c, hipGetLastError());
+        GK_TRY_HIP(c, hipMemcpyAsync(c->vals[1], c->vals[0], 4 * s.nA, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return split_done(c, keys ? 1 : c->cur, c->heads, keys, keys_final);
+}
+
+// the interleave of the sorted A (vals[0], c->heads) and B runs into vals[1], hd and, with W key words,
+// keys[1]; PK: A's keys from the packed sequence pk.  (A kernel reads only the arguments its W and PK use.)
+template <int W, bool PK>
+static void launch_merge(gk_ctx *c, const KeySpec &ks, const SplitState &s, const uint32_t *pos,
+                         const uint32_t *g_first, uint64_t G, uint8_t *hd, const uint64_t *pk) {
+    const dim3 ga((unsigned)((s.nA + kMTile - 1) / kMTile)), gb((unsigned)((s.nB + kMTile - 1) / kMTile));
+    hipLaunchKernelGGL((merge_a_kernel<W, PK>), ga, dim3(kMT), 0, c->stream, c->vals[0], c->heads, s.nA, pos, g_first,
+                       G, s.nB, c->vals[1], hd, s.a_keys, s.k, c->keys[1], pk, ks.canonical);
+    hipLaunchKernelGGL(merge_b_kernel<W>, gb, dim3(kMT), 0, c->stream, s.b_st[s.bres], s.b_heads, s.nB, pos, g_first,
+                       G, c->vals[1], hd, s.b_keys, s.nA + s.nB, c->keys[1]);
+}
+
+// 4. merge: B groups, their insertion points in A, the interleave into vals[1] + heads
+static int merge(gk_ctx *c, const KeySpec &ks, const SplitState &s, bool *keys_final) {
+    int slot;
     timer_begin(c, "split_merge", &slot);
     uint32_t *g_first, *pos;
     uint64_t G = 0;
-    GK_TRY_HIP(c, scratch(c, "split_g_first", nB + 64, &g_first));
-    GK_TRY_HIP(c, select_flags(c, b_heads, nB, g_first, &G));
+    GK_TRY_HIP(c, scratch(c, "split_g_first", s.nB + 64, &g_first));
+    GK_TRY_HIP(c, select_flags(c, s.b_heads, s.nB, g_first, &G));
     GK_TRY_HIP(c, scratch(c, "split_pos", G + 64, &pos));
-    hipLaunchKernelGGL(b_group_pos_kernel, dim3(grid_of_n(G)), dim3(256), 0, c->stream, c->sba, k, ks.canonical,
-                       c->vals[0], nA, b_st[bres], g_first, G, pos);
+    hipLaunchKernelGGL(b_group_pos_kernel, dim3(grid_of_n(G)), dim3(256), 0, c->stream, c->sba, s.k, ks.canonical,
+                       c->vals[0], s.nA, s.b_st[s.bres], g_first, G, pos);
     GK_TRY_HIP(c, hipGetLastError());
     uint8_t *hd;
-    GK_TRY_HIP(c, scratch(c, "split_heads", n + 64, &hd));
-    if (WK) {  // (a no-op after the pre-sizing above; a_keys / b_keys never live in keys[1])
-        if (a_keys == c->keys[1] || b_keys == c->keys[1])
+    GK_TRY_HIP(c, scratch(c, "split_heads", s.n + 64, &hd));
+    if (s.WK) {  // (a no-op after the pre-sizing in sort_a; a_keys / b_keys never live in keys[1])
+        if (s.a_keys == c->keys[1] || s.b_keys == c->keys[1])
             return fail(c, GK_E_STATE, "split sort: input keys alias the merge output buffer");
-        int r = grow_key_buffer(c, 1, WK);
-        if (r != GK_OK) return r;
+        if (int r = grow_key_buffer(c, 1, s.WK)) return r;
     }
-    const dim3 ga((unsigned)((nA + kMTile - 1) / kMTile)), gb((unsigned)((nB + kMTile - 1) / kMTile));
-    uint64_t *ok = c->keys[1];
-    if (a_packed) {
+    const uint64_t *pk = nullptr;
+    if (s.a_packed) {
         // the 2-bit packed sequence: three words past every start (the sba's '$' pad covers them)
         // (the transfer's resident packed copy when there is one: the same codes at every position)
-        const uint64_t nwords = (L + kSbaPad) / 32;
-        const uint64_t *pk = c->res_pk ? c->res_code : nullptr;
+        const uint64_t nwords = (c->sba_len + kSbaPad) / 32;
+        pk = c->res_pk ? c->res_code : nullptr;
         if (!pk) {
             uint64_t *own;
             GK_TRY_HIP(c, scratch(c, "split_pk", nwords, &own));
@@ -1047,51 +1023,47 @@ int split_sort(gk_ctx *c, const KeySpec &ks, bool *used, const SplitRange *rg) {
             GK_TRY_HIP(c, hipGetLastError());
             pk = own;
         }
-#define GK_MERGE_PK(W_)                                                                                         \
-    do {                                                                                                        \
-        hipLaunchKernelGGL((merge_a_kernel<W_, true>), ga, dim3(kMT), 0, c->stream, c->vals[0], c->heads, nA,     \
-                           pos, g_first, G, nB, c->vals[1], hd, nullptr, k, ok, pk, ks.canonical);               \
-        hipLaunchKernelGGL(merge_b_kernel<W_>, gb, dim3(kMT), 0, c->stream, b_st[bres], b_heads, nB, pos,         \
-                           g_first, G, c->vals[1], hd, b_keys, nA + nB, ok);                                     \
-    } while (0)
-        if (WK == 3) GK_MERGE_PK(3);
-        else if (WK == 4) GK_MERGE_PK(4);
-        else return fail(c, GK_E_STATE, "split sort: packed-sequence keys need 3 or 4 key words");
-#undef GK_MERGE_PK
-        GK_TRY_HIP(c, hipGetLastError());
-        c->split_keys_final = true;
-        timer_end(c, slot);
-        c->cur = 1;
-        c->heads = hd;
-        c->heads_valid = true;
-        return GK_OK;
     }
-    switch (WK) {
-    case 0:
-        hipLaunchKernelGGL(merge_a_kernel<0>, ga, dim3(kMT), 0, c->stream, c->vals[0], c->heads, nA, pos, g_first, G,
-                           nB, c->vals[1], hd, nullptr, k, nullptr);
-        hipLaunchKernelGGL(merge_b_kernel<0>, gb, dim3(kMT), 0, c->stream, b_st[bres], b_heads, nB, pos, g_first, G,
-                           c->vals[1], hd, nullptr, n, nullptr);
-        break;
-    case 1:
-        hipLaunchKernelGGL(merge_a_kernel<1>, ga, dim3(kMT), 0, c->stream, c->vals[0], c->heads, nA, pos, g_first, G,
-                           nB, c->vals[1], hd, a_keys, k, ok);
-        hipLaunchKernelGGL(merge_b_kernel<1>, gb, dim3(kMT), 0, c->stream, b_st[bres], b_heads, nB, pos, g_first, G,
-                           c->vals[1], hd, b_keys, nA + nB, ok);
-        break;
-    default:
-        hipLaunchKernelGGL(merge_a_kernel<2>, ga, dim3(kMT), 0, c->stream, c->vals[0], c->heads, nA, pos, g_first, G,
-                           nB, c->vals[1], hd, a_keys, k, ok);
-        hipLaunchKernelGGL(merge_b_kernel<2>, gb, dim3(kMT), 0, c->stream, b_st[bres], b_heads, nB, pos, g_first, G,
-                           c->vals[1], hd, b_keys, nA + nB, ok);
-    }
+    if (s.a_packed && s.WK == 3) launch_merge<3, true>(c, ks, s, pos, g_first, G, hd, pk);
+    else if (s.a_packed && s.WK == 4) launch_merge<4, true>(c, ks, s, pos, g_first, G, hd, pk);
+    else if (s.a_packed) return fail(c, GK_E_STATE, "split sort: packed-sequence keys need 3 or 4 key words");
+    else if (s.WK == 0) launch_merge<0, false>(c, ks, s, pos, g_first, G, hd, pk);
+    else if (s.WK == 1) launch_merge<1, false>(c, ks, s, pos, g_first, G, hd, pk);
+    else launch_merge<2, false>(c, ks, s, pos, g_first, G, hd, pk);
     GK_TRY_HIP(c, hipGetLastError());
-    c->split_keys_final = WK > 0;
     timer_end(c, slot);
-    c->cur = 1;
-    c->heads = hd;
-    c->heads_valid = true;
-    return GK_OK;
+    return split_done(c, 1, hd, s.WK > 0, keys_final);
+}
+
+// The file header's algorithm, stage by stage.  rg: a key-range shard's share of the k-mers (gk_shard_sort_range).
+int split_sort(gk_ctx *c, const KeySpec &ks, bool *used, bool *keys_final, const SplitRange *rg) {
+    *used = *keys_final = false;
+    SplitState s;
+    s.k = ks.symbols;
+    s.n = rg ? c->sba_len : c->n;  // key-range shards: the k-mer count is not known yet (<= L)
+    if (s.k > 64 || ks.bits != 4 || ks.lenbits || ks.symbols != ks.min_len) return GK_OK;
+    if (rg && s.k < rg->pns) return fail(c, GK_E_ARG, "split: key-range shards need k >= the prefix length");
+    GK_TRY_HIP(c, split_tables());
+    // final keys: the sorted order leaves with its W-word 4-bit keys and needs no re-encode -- B's from their
+    // own sort, A's written by the merge: expanded from the one-word 2-bit MSD keys (k <= 32), or read from a
+    // 2-bit packed copy of the sequence (k <= 63; GKM_NO_MERGE_KEYS=1: the re-encode after the sort instead)
+    s.a_packed = s.k > 32 && s.k <= 63 && !opt("GKM_NO_MERGE_KEYS");
+    s.WK = s.k <= 32 || s.a_packed ? ks.words : 0;
+    // 1. class B starts: homopolymers (one letter k times) apart from the rest
+    int rc = rg && rg->given ? select_given(c, ks, *rg, &s)
+                             : class_b_select(c, ks, 0, c->sba_len, rg, &s.b_st[0], &s.nR, &s.h_st, &s.nH);
+    if (rc != GK_OK) return rc;
+    s.nB = s.nR + s.nH;
+    if (s.nB > s.n) return fail(c, GK_E_HIP, "split: more class-B k-mers than k-mers");
+    if (!rg && s.nB * 4 > s.n) return GK_OK;  // mostly non-ACGT k-mers: the plain 4-bit MSD is the better sort
+    *used = true;
+    s.nA = rg ? 0 : s.n - s.nB;  // (key-range shards: sort_a finds it)
+    if ((rc = sort_b_rest(c, ks, rg != nullptr, &s)) != GK_OK) return rc;
+    if (s.nH > 0 && (rc = splice_homopolymers(c, ks, &s)) != GK_OK) return rc;
+    if ((rc = sort_a(c, ks, rg, &s)) != GK_OK) return rc;
+    if (s.nA == 0) return finish_only_b(c, s, keys_final);
+    if (s.nB == 0) return finish_only_a(c, s, keys_final);
+    return merge(c, ks, s, keys_final);
 }
 
 }  // namespace gkm

@@ -718,8 +718,11 @@ def _split_keys_check(seqs, k, canonical=False):
 
 @pytest.mark.parametrize("k", [5, 20, 31])
 def test_split_only_class_b_kmers_keys(k):
-    """Every k-mer holds a non-ACGT letter (the split sort has no class-A k-mer): the keys come from
-    the B sort and the homopolymer groups' constant keys."""
+    """Every k-mer holds a non-ACGT letter.  The split sort selects its class B, finds it to be more than a
+    quarter of the k-mers (here: all of them) and returns unused; the plain 4-bit MSD sorts the
+    enumeration, and the keys are its own (one word) or re-encoded after it (k = 20, 31).  A profile
+    report of this input shows split_b_select and msd_total, and no split_b_encode, split_b_homo or
+    split_merge."""
     rng = np.random.default_rng(80 + k)
     s = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 20_000)].copy()
     s[::max(2, k // 2)] = ord("N")  # a non-ACGT byte in every window

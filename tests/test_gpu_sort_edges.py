@@ -212,12 +212,18 @@ def test_mixed_runs_edges(k, builder, T, canonical, monkeypatch):
 
 
 @pytest.mark.parametrize("canonical", [False, True], ids=["fwd", "canon"])
-def test_mixed_runs_k3(canonical, monkeypatch):
-    """k = 3: 12-bit 4-bit keys, the class-A keys narrower than the 7-bit L0 digit; the key-range
-    shards take no split below k = 4 (gkm_shard.hip range_split), gk_sort decides by the class-B share"""
-    tag = f"mixed {'canonical' if canonical else 'forward'} k=3"
-    for r in reference("runs", 3, T_FLAG, canonical, False):
-        sort_and_check(load(r, monkeypatch), r, 3, canonical, False, tag)
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_mixed_runs_k3(k, canonical, monkeypatch):
+    """k <= 3: 4-bit keys of at most 12 bits, the class-A keys narrower than the 7-bit L0 digit; the
+    key-range shards take no split below k = 4 (gkm_shard.hip range_split), gk_sort decides by the
+    class-B share.  k = 1: every class-B k-mer is a homopolymer, so the split sort has no B starts to
+    sort and goes from the select to the homopolymer splice; k = 2, 3: the select kernel's short-k
+    branches"""
+    tag = f"mixed {'canonical' if canonical else 'forward'} k={k}"
+    timers = set()
+    for r in reference("runs", k, T_FLAG, canonical, False):
+        sort_and_check(load(r, monkeypatch), r, k, canonical, False, tag, timers)
+    assert {"split_b_select", "split_merge", "split_b_homo"} <= timers, (tag, sorted(timers))  # the split sort ran
 
 
 # ---------------------------------------------------------------------------------------------
