@@ -53,6 +53,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_SCREEN_PATH", false},     {"GKM_SCREEN_CHUNK", false},
     // gk_lcp (gkm_lcp.hip): forced path (bytes | keys)
     {"GKM_LCP_PATH", false},
+    // gk_match (gkm_match.hip): forced path (bytes | keys), bytes of reads per launch
+    {"GKM_MATCH_PATH", false},      {"GKM_MATCH_CHUNK", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)

@@ -14,7 +14,7 @@
 //          codes; canonical orders compare canonical forms on both sides.  Always valid.  The search
 //          and the comparison are gkm_bytes_search.h's (gk_lookup's and gk_join's), the window read
 //          in place; a byte outside the alphabet in it is code 0 and fails the call.
-// A tile finds the sequences of its first and last position by a search over `offsets` that the 64
+// (gkm_tile_seqs.h, shared with gk_match:) A tile finds the sequences of its first and last position by a search over `offsets` that the 64
 // lanes of one wave share, keeps the boundaries between them in LDS (kScreenBounds at a time: a tile
 // with more -- many empty or very short reads -- takes them in several passes), sums per sequence in
 // LDS and issues one global atomic per (block, sequence) and counter.
@@ -26,6 +26,7 @@
 #include "gkm_internal.h"
 #include "gkm_lookup_search.h"
 #include "gkm_screen_host.h"
+#include "gkm_tile_seqs.h"
 
 #ifndef GKM_SCREEN_WIN
 // windows per thread: 2, 4 and 8 measured within the run-to-run spread of one another at C3 size
@@ -62,24 +63,6 @@ struct ScreenArgs {
     unsigned long long *bad;        // smallest position of a byte outside the alphabet
 };
 
-// first u in [lo, hi] with off[u] > g, given off[hi] > g and off[u] <= g for every u < lo; called by
-// all 64 lanes of a wave, which probe 64 evenly spaced entries per round
-__device__ __forceinline__ uint64_t wave_upper_bound(const uint64_t *__restrict__ off, uint64_t lo, uint64_t hi,
-                                                     uint64_t g, int lane) {
-    while (lo < hi) {
-        const uint64_t stride = (hi - lo) / 64 + 1;
-        const uint64_t x = lo + (uint64_t)lane * stride;
-        const bool above = x >= hi || off[x] > g;
-        const unsigned long long m = __ballot(above);
-        const int f = m ? __ffsll((long long)m) - 1 : 64;  // the first lane whose entry is above g
-        if (f == 0) return lo;
-        const uint64_t top = lo + (uint64_t)f * stride;
-        lo = lo + (uint64_t)(f - 1) * stride + 1;
-        hi = top < hi ? top : hi;
-    }
-    return lo;
-}
-
 // sign of (reverse complement of q) - q over K symbols in 4-bit codes
 __device__ __forceinline__ int rc_sign(const uint8_t *__restrict__ q, int K, const uint8_t *lut4) {
     for (int t = 0; t < K; ++t) {
@@ -106,18 +89,7 @@ __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs
     const uint64_t t0 = blockIdx.x * (uint64_t)kScreenTile;  // in the chunk
     const uint64_t t1 = t0 + kScreenTile < a.nslots ? t0 + kScreenTile : a.nslots;
     const uint64_t g0 = a.base + t0, g1 = a.base + t1;       // in the batch
-    if (tid < 64) {  // the sequences of the tile's first and last position
-        const uint64_t u0 = wave_upper_bound(a.offsets, 0, a.nseq, g0, tid);
-        uint64_t lo = u0, hi = a.nseq;
-        const uint64_t near = u0 + 63 < a.nseq ? u0 + 63 : a.nseq;  // (mostly a few sequences on)
-        if (a.offsets[near] > g1 - 1) hi = near;
-        else lo = near + 1;
-        const uint64_t u1 = wave_upper_bound(a.offsets, lo, hi, g1 - 1, tid);
-        if (tid == 0) {
-            s_j[0] = u0 - 1;
-            s_j[1] = u1 - 1;
-        }
-    }
+    if (tid < 64) tile_seq_span(a.offsets, a.nseq, g0, g1, tid, s_j);  // the tile's first and last sequence
     __syncthreads();
     // the alphabet check of the positions the tile owns; the key path's staging with its halo
     if (MODE == 0) {
@@ -140,30 +112,14 @@ __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs
     const uint64_t pt0 = g0 + (uint64_t)tid * W;  // this thread's run of positions
     const uint64_t pt1 = pt0 + W < g1 ? pt0 + W : g1;
     const uint64_t mask = K >= 32 ? ~0ull : (1ull << (2 * K)) - 1;
-    uint64_t ja = j0, slab_lo = g0;
-    for (;;) {  // passes of up to kScreenBounds sequences
-        const uint64_t jb = j1 - ja < (uint64_t)kScreenBounds ? j1 : ja + kScreenBounds - 1;
-        const int cnt = (int)(jb - ja + 1);
-        for (int i = tid; i < cnt; i += kScreenThreads) {
-            s_tab[i] = a.offsets[ja + 1 + i];
-            s_pres[i] = 0;
-            s_occ[i] = 0;
-        }
-        __syncthreads();
-        const uint64_t last = s_tab[cnt - 1];
-        const uint64_t slab_hi = last < g1 ? last : g1;  // the pass's positions: [slab_lo, slab_hi)
+    auto init = [&](int i) {
+        s_pres[i] = 0;
+        s_occ[i] = 0;
+    };
+    auto body = [&](uint64_t, int cnt, uint64_t slab_lo, uint64_t slab_hi) {
         const uint64_t pa = slab_lo > pt0 ? slab_lo : pt0, pb = slab_hi < pt1 ? slab_hi : pt1;
         if (pa < pb) {
-            int jr;  // the sequence of pa in the pass: the first end above pa
-            {
-                int lo = 0, hi = cnt - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_tab[mid] <= pa) lo = mid + 1;
-                    else hi = mid;
-                }
-                jr = lo;
-            }
+            int jr = pass_seq_of(s_tab, cnt, pa);  // the sequence of pa in the pass
             const int m = (int)(pb - pa);
             int cur = jr;
             uint32_t pres = 0;
@@ -255,16 +211,12 @@ __global__ __launch_bounds__(kScreenThreads) void screen_kernel(const ScreenArgs
             }
             flush();
         }
-        __syncthreads();
-        for (int i = tid; i < cnt; i += kScreenThreads) {  // one atomic per (block, sequence) and counter
-            if (s_pres[i]) atomicAdd(&a.present[ja + i], s_pres[i]);
-            if (s_occ[i]) atomicAdd(&a.occ[ja + i], s_occ[i]);
-        }
-        if (jb == j1) break;
-        ja = jb + 1;
-        slab_lo = slab_hi;
-        __syncthreads();
-    }
+    };
+    auto flush_seq = [&](int i, uint64_t j) {
+        if (s_pres[i]) atomicAdd(&a.present[j], s_pres[i]);
+        if (s_occ[i]) atomicAdd(&a.occ[j], s_occ[i]);
+    };
+    tile_seq_passes<kScreenBounds, kScreenThreads>(a.offsets, j0, j1, g0, g1, s_tab, tid, init, body, flush_seq);
 }
 
 }  // namespace gkm

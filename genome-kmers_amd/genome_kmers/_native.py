@@ -61,6 +61,7 @@ EXPORTED = (
     "gk_join", "gk_copy_join", "gk_device_join", "gk_join_mask",
     "gk_screen",
     "gk_lcp", "gk_copy_lcp", "gk_device_lcp", "gk_lcp_spectrum", "gk_position_track", "gk_device_track",
+    "gk_match",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
@@ -176,6 +177,8 @@ _SIGS = {
     "gk_device_join": ([_P, ctypes.POINTER(_P), ctypes.POINTER(_P), _U64P], ctypes.c_int),
     "gk_join_mask": ([_P, ctypes.c_int], ctypes.c_int),
     "gk_screen": ([_P, _U8P, _U64P, ctypes.c_uint64, ctypes.c_uint32, _U32P, _U64P, _U32P], ctypes.c_int),
+    "gk_match": ([_P, _U8P, _U64P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P, _U64P, _U32P,
+                  _U64P, _U32P], ctypes.c_int),
     "gk_lcp": ([_P, ctypes.c_uint32, _U64P], ctypes.c_int),
     "gk_copy_lcp": ([_P, ctypes.c_uint64, _U32P, ctypes.c_uint64], ctypes.c_int),
     "gk_device_lcp": ([_P, ctypes.POINTER(_P), _U64P], ctypes.c_int),
@@ -699,6 +702,35 @@ class Engine:
                                            _ptr(occurrences, ctypes.c_uint64),
                                            _ptr(wc, ctypes.c_uint32) if per_window else None))
         return n_present, occurrences, wc
+
+    # ---- matching statistics of reads (gk_match) ------------------------------------------------
+    def match(self, seqs: np.ndarray, offsets: np.ndarray, max_len: int = 0, per_position=True):
+        """(longest uint32[nseq], longest_pos uint32[nseq], sum_len uint64[nseq], lengths uint32[total],
+        first uint64[total], count uint32[total]) of a pack_sequences batch against the sorted order
+        (gk_match); max_len 0: the sort length.  ``per_position``: True or False for all three
+        per-position arrays, or three flags (lengths, first, count); an array not asked for is None."""
+        arr = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if arr.ndim != 1 or off.ndim != 1 or off.size == 0:
+            raise ValueError("match takes a 1-D uint8 array and its nseq + 1 offsets")
+        want = (bool(per_position),) * 3 if isinstance(per_position, (bool, np.bool_)) else tuple(map(bool, per_position))
+        if len(want) != 3:
+            raise ValueError("per_position is a bool or three of them (lengths, first, count)")
+        nseq = off.size - 1
+        longest = np.zeros(nseq, dtype=np.uint32)
+        longest_pos = np.zeros(nseq, dtype=np.uint32)
+        sum_len = np.zeros(nseq, dtype=np.uint64)
+        lengths = np.zeros(arr.size, dtype=np.uint32) if want[0] else None
+        first = np.zeros(arr.size, dtype=np.uint64) if want[1] else None
+        count = np.zeros(arr.size, dtype=np.uint32) if want[2] else None
+        if nseq:
+            self._check(self.lib.gk_match(self.ctx, _ptr(arr, ctypes.c_uint8), _ptr(off, ctypes.c_uint64), nseq,
+                                          int(max_len), 0, _ptr(longest, ctypes.c_uint32),
+                                          _ptr(longest_pos, ctypes.c_uint32), _ptr(sum_len, ctypes.c_uint64),
+                                          _ptr(lengths, ctypes.c_uint32) if want[0] else None,
+                                          _ptr(first, ctypes.c_uint64) if want[1] else None,
+                                          _ptr(count, ctypes.c_uint32) if want[2] else None))
+        return longest, longest_pos, sum_len, lengths, first, count
 
     # ---- the LCP array of the sorted order (gk_lcp) -------------------------------------------
     def lcp(self, max_len: int) -> np.ndarray:

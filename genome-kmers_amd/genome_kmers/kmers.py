@@ -38,6 +38,34 @@ NEVER_UNIQUE = _native.NEVER_UNIQUE  # min_unique_lengths: not unique at any len
 # the windows' counts; with per_window=True also the count per byte position and the reads' offsets
 ScreenResult = namedtuple("ScreenResult", ("n_windows", "n_present", "occurrences", "window_counts", "offsets"),
                           defaults=(None, None))
+# Kmers.match_lengths' result: per read the longest match, the offset in the read of the first position
+# that attains it and the sum of the positions' match lengths; with per_position=True also, per byte of
+# the batch, the match length and its range of sorted positions, and the reads' offsets
+MatchResult = namedtuple("MatchResult", ("longest", "longest_pos", "sum_len", "lengths", "first", "count", "offsets"),
+                         defaults=(None, None, None, None))
+MAX_MATCH_LEN = 4096  # the largest max_len of match_lengths when max_kmer_len is None
+
+
+def maximal_from_lengths(lengths, offsets, min_len):
+    """The maximal matches among per-position match lengths (``MatchResult.lengths`` and ``.offsets``):
+    ``(read, pos, length)`` arrays (int64, int64, uint32) in batch order.  Position p of a read is
+    reported iff ``lengths[p] >= min_len`` and p is the read's first position or
+    ``lengths[p - 1] < lengths[p] + 1``: the match at p is not merely the tail of the match at p - 1.
+    NumPy on the host, O(total bases)."""
+    lengths = np.asarray(lengths)
+    offsets = np.asarray(offsets).astype(np.int64)
+    if lengths.ndim != 1 or offsets.ndim != 1 or offsets.size == 0 or int(offsets[-1]) != lengths.size:
+        raise ValueError("maximal_from_lengths takes the per-position lengths and the reads' nseq + 1 offsets "
+                         f"(lengths: {lengths.shape}, offsets: {offsets.shape})")
+    v = lengths.astype(np.int64)
+    keep = v >= int(min_len)
+    if v.size:
+        keep[1:] &= v[:-1] < v[1:] + 1
+        first = offsets[:-1][offsets[:-1] < offsets[1:]]  # the first position of every non-empty read
+        keep[first] = v[first] >= int(min_len)
+    at = np.flatnonzero(keep)
+    read = np.searchsorted(offsets, at, side="right") - 1
+    return read.astype(np.int64), (at - offsets[read]).astype(np.int64), lengths[at].astype(np.uint32)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -935,6 +963,67 @@ class Kmers:
         if per_window:
             return ScreenResult(n_windows, n_present, occurrences, wc, off)
         return ScreenResult(n_windows, n_present, occurrences)
+
+    # ---- matching statistics of reads (no reference counterpart) -------------------------------
+    def _match_checks(self, what, max_len):
+        """The preconditions of gk_match, checked on the host before any device call; returns the
+        max_len to pass on (0: the sort length)."""
+        if not self._is_sorted:
+            raise AssertionError(f"The kmers must be sorted when calling {what}")
+        if self.kmer_source_strand != "forward":
+            raise ValueError(f"{what} needs kmer_source_strand 'forward' ({self.kmer_source_strand!r})")
+        if getattr(self, "_canonical", False):
+            raise ValueError(f"{what} needs a forward order: canonical k-mers have no prefixes (canonical: True)")
+        if max_len is None:
+            if self.max_kmer_len is None:
+                raise ValueError(f"{what} needs max_len when max_kmer_len is None (the suffix order has no "
+                                 f"length of its own; max_len: None)")
+            return 0
+        if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)):
+            raise ValueError(f"max_len must be an int >= 1 (max_len: {max_len!r})")
+        if max_len < 1:
+            raise ValueError(f"max_len ({max_len}) must be >= 1")
+        if self.max_kmer_len is not None and max_len > self.max_kmer_len:
+            raise ValueError(f"max_len ({max_len}) is greater than max_kmer_len ({self.max_kmer_len})")
+        if self.max_kmer_len is None and max_len > MAX_MATCH_LEN:
+            raise ValueError(f"max_len ({max_len}) is greater than {MAX_MATCH_LEN}, the largest cap when "
+                             f"max_kmer_len is None")
+        return int(max_len)
+
+    def match_lengths(self, seqs, max_len: Union[int, None] = None, per_position: bool = True) -> MatchResult:
+        """How far each read matches the index from every position on: matching statistics, answered
+        on the GPU (gk_match).
+
+        ``seqs`` as in ``screen``.  For every byte position p of a read, ``lengths[p]`` is the length
+        of the longest prefix of ``read[p:]`` -- at most ``max_len`` -- that ``find`` finds (count
+        above 0), and ``first[p]``, ``count[p]`` are ``find``'s answer for that prefix (0, 0 where the
+        length is 0).  A match never crosses the end of a read or of a contig.  ``max_len`` defaults
+        to max_kmer_len and may not exceed it; when max_kmer_len is None it must be given, at most
+        4096.  Returns ``MatchResult``: per read ``longest`` (uint32), ``longest_pos`` (uint32: the
+        offset in the read of the first position that attains it) and ``sum_len`` (uint64); with
+        ``per_position`` also ``lengths`` (uint32), ``first`` (uint64), ``count`` (uint32) per byte of
+        the batch and the reads' ``offsets``.  Not available after sort(canonical=True); for the
+        other strand pass the reverse-complemented reads."""
+        cap = self._match_checks("match_lengths", max_len)
+        arr, off = _native.pack_sequences(seqs)
+        self._sync_device()
+        longest, longest_pos, sum_len, lengths, first, count = self._engine.match(arr, off, cap, bool(per_position))
+        if per_position:
+            return MatchResult(longest, longest_pos, sum_len, lengths, first, count, off)
+        return MatchResult(longest, longest_pos, sum_len)
+
+    def maximal_matches(self, seqs, min_len: int, max_len: Union[int, None] = None) -> tuple:
+        """The maximal exact matches of a batch of reads, at least ``min_len`` long: arrays
+        ``(read, pos, length, first, count)`` -- the read, the offset in it, the match's length (capped
+        at ``max_len`` as in ``match_lengths``) and its sorted positions ``[first, first + count)``,
+        whose locations follow as for ``find`` (gk_locate).  A position is reported when its match is
+        not merely the tail of the match one position before (maximal_from_lengths)."""
+        if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or min_len < 1:
+            raise ValueError(f"min_len must be an int >= 1 (min_len: {min_len!r})")
+        res = self.match_lengths(seqs, max_len, per_position=True)
+        read, pos, length = maximal_from_lengths(res.lengths, res.offsets, min_len)
+        at = res.offsets.astype(np.int64)[read] + pos
+        return read, pos, length, res.first[at], res.count[at]
 
     # ---- the LCP array, the spectrum and the position tracks (no reference counterpart) ---------
     def _lcp_checks(self, what, length, name="max_len"):

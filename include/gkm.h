@@ -461,6 +461,39 @@ int gk_lcp_spectrum(gk_ctx *ctx, uint32_t max_len, uint64_t *distinct, uint64_t 
 int gk_position_track(gk_ctx *ctx, int kind, uint32_t len, uint32_t *dst, uint64_t sba_len);
 int gk_device_track(gk_ctx *ctx, void **track, uint64_t *sba_len);
 
+/* Matching statistics of a batch of reads against the sorted index (no reference routine: the reference
+ * offers no search; equality and order are gk_lookup's, by its compare_sba_kmers_lexicographically,
+ * kmers.py:306-397).  seqs and offsets are gk_screen's batch, with its rules and its checks made before
+ * any byte of seqs is read; the bytes are letters of the sba alphabet without '$'.  K is the sort length.
+ * The cap C: after a bounded sort max_len is 0 (meaning K) or in 1..K; after a sort with max_kmer_len
+ * None it is required and in 1..4096.  Longer matches are reported as C.
+ * For byte position p of a sequence that ends at e let m = min(C, e - p).  match_len[p] = the largest l
+ * in 0..m for which gk_lookup of the l bytes at p (qlen = l) has count > 0 (presence is monotone in l);
+ * match_first[p], match_count[p] = gk_lookup's first and count for that l, both 0 when l = 0.  A match
+ * never crosses the end of a read or of a contig; letters compare by byte equality ('N' matches 'N').
+ * Each of the three per-position arrays may be NULL (else offsets[nseq] entries): an array that is not
+ * asked for costs no device memory and no copy.
+ * longest[j] = the maximum of match_len over sequence j's positions, longest_pos[j] = the offset in the
+ * sequence of the first position that attains it (0 when longest[j] is 0 or the sequence is empty),
+ * sum_len[j] = the sum of match_len.  Integer results, the same on every run and on both paths.
+ * Each byte crosses to the device once, in chunks that overlap by C - 1 bytes.  Two paths with the same
+ * answers: the sorted one-word 2-bit keys when the context holds them (A/C/G/T-only index, K <= 32,
+ * forward order, min_kmer_len == K; a match ends at any other letter of a read), else one search per
+ * position over the sorted starts comparing sequence bytes (mixed alphabets, K > 32, k-mers cut short by
+ * contig ends, None, rank-key orders); GKM_MATCH_PATH = bytes | keys (gk_set_option) forces one, keys
+ * where it does not apply: GK_E_UNSUPPORTED.  GKM_MATCH_CHUNK lowers the bytes of reads per launch.
+ * Synchronises the stream; leaves the sorted order, the unique view, a join result and the LCP view as
+ * they are.
+ * GK_E_STATE: no sequence, or not sorted; GK_E_UNSUPPORTED: a canonical order (no prefixes); GK_E_ARG: a
+ * null context or required array, flags != 0 (there are none yet), max_len above K, max_len 0 or above
+ * 4096 after None, offsets that do not start at 0 or decrease, a sequence over 2^32 - 1 bytes;
+ * GK_E_ALPHABET: a byte outside the alphabet (found on the device; gk_screen's message; the outputs are
+ * then unspecified).  Each message names the values.  nseq == 0 returns GK_OK and touches nothing; a
+ * total length of 0 writes zeros to the per-sequence outputs. */
+int gk_match(gk_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint64_t nseq, uint32_t max_len,
+             uint32_t flags, uint32_t *longest, uint32_t *longest_pos, uint64_t *sum_len,
+             uint32_t *match_len, uint64_t *match_first, uint32_t *match_count);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
