@@ -55,6 +55,8 @@ constexpr Knob kKnobs[] = {
     {"GKM_LCP_PATH", false},
     // gk_match (gkm_match.hip): forced path (bytes | keys), bytes of reads per launch
     {"GKM_MATCH_PATH", false},      {"GKM_MATCH_CHUNK", false},
+    // gk_minimizers (gkm_minimizer.hip): positions a chunk owns
+    {"GKM_MINIMIZER_CHUNK", false},
 };
 const Knob *find_knob(const char *name) {
     for (const Knob &k : kKnobs)
@@ -128,7 +130,8 @@ extern "C" void gk_destroy(gk_ctx *c) {
     if (c->pre_stream) hipStreamDestroy(c->pre_stream);
     void *bufs[] = {c->sba, c->seg, c->res_code, c->res_dol, c->vals[0], c->vals[1], c->keys[0], c->keys[1], c->status, c->counters,
                     c->hist, c->offsets, c->flags, c->idx_a, c->idx_b, c->ucount, c->cumk, c->tile_sums, c->scalars,
-                    c->dhist, c->mask, c->hmask, c->ranks, c->ym, c->yoff, c->oy, c->ot, c->onum};
+                    c->dhist, c->mask, c->hmask, c->ranks, c->ym, c->yoff, c->oy, c->ot, c->onum,
+                    c->mz_pos, c->mz_key, c->mz_strand};
     for (void *b : bufs)
         if (b) dev_free(b);
     for (auto &e : c->scratch)

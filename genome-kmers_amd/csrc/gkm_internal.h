@@ -195,6 +195,14 @@ struct gk_ctx {
     uint32_t lcp_asked = 0;    // the max_len of the last gk_lcp: what gk_copy_lcp clamps to
     uint64_t track_len = 0;    // entries of the last position track (scratch "track"), 0: none
 
+    // gk_minimizers' result (gkm_minimizer.hip): positions in the batch, canonical keys and strands of
+    // the selected k-mers, mz_n of each in buffers of mz_cap; no view of the k-mer set or its order, so
+    // nothing drops it but the next gk_minimizers
+    uint64_t *mz_pos = nullptr, *mz_key = nullptr;
+    uint8_t *mz_strand = nullptr;
+    uint64_t mz_cap = 0, mz_n = 0;
+    bool mz_valid = false;
+
     // gk_lookup's prefix directory over keys[cur] (gkm_lookup.hip; scratch "lookup_dir"): built by the
     // first key-path lookup after a sort, dropped with the order's views (drop_order_views) and with the
     // key buffers (ensure_elems)

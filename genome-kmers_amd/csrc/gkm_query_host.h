@@ -1,4 +1,5 @@
-// gkm_query_host.h -- how gk_lookup, gk_lookup_mismatch, gk_join, gk_screen and gk_match read their knobs.
+// gkm_query_host.h -- how gk_lookup, gk_lookup_mismatch, gk_join, gk_screen, gk_match and gk_minimizers read
+// their knobs.
 // Plain C++ (no HIP): the stand-alone drivers run it under the host sanitizers (tests/sanitize).
 #pragma once
 

@@ -7,6 +7,8 @@
 // BOUNDS (tile_seq_passes): a pass keeps its sequences' ends in LDS, the caller sums per sequence in
 // LDS tables of its own and issues one global atomic per (block, sequence) and counter.  A tile with
 // more than BOUNDS sequences -- many empty or very short reads -- takes several passes.
+// gk_minimizers (gkm_minimizer.hip) uses tile_seq_span alone: it marks the sequence starts between the
+// two ends in its staged tile and keeps no table.
 #pragma once
 
 #include <hip/hip_runtime.h>

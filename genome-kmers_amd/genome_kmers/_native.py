@@ -62,6 +62,7 @@ EXPORTED = (
     "gk_screen",
     "gk_lcp", "gk_copy_lcp", "gk_device_lcp", "gk_lcp_spectrum", "gk_position_track", "gk_device_track",
     "gk_match",
+    "gk_minimizers", "gk_copy_minimizers", "gk_device_minimizers", "gk_select_minimizers",
 )
 
 SORT_CANONICAL = 1  # GK_SORT_CANONICAL
@@ -71,6 +72,8 @@ MISMATCH_BOTH_STRANDS = 1  # GK_MISMATCH_BOTH_STRANDS
 JOIN_KEEP_ABSENT = 1  # GK_JOIN_KEEP_ABSENT
 JOIN_KEEP_PRESENT = 2  # GK_JOIN_KEEP_PRESENT
 SCREEN_BOTH_STRANDS = 1  # GK_SCREEN_BOTH_STRANDS
+MINIMIZER_CANONICAL = 1  # GK_MINIMIZER_CANONICAL
+MINIMIZER_LEX = 2  # GK_MINIMIZER_LEX
 NEVER_UNIQUE = 0xFFFFFFFF  # GK_NEVER_UNIQUE
 TRACK_MIN_UNIQUE = 1  # GK_TRACK_MIN_UNIQUE
 TRACK_MULTIPLICITY = 2  # GK_TRACK_MULTIPLICITY
@@ -185,6 +188,11 @@ _SIGS = {
     "gk_lcp_spectrum": ([_P, ctypes.c_uint32, _U64P, _U64P], ctypes.c_int),
     "gk_position_track": ([_P, ctypes.c_int, ctypes.c_uint32, _U32P, ctypes.c_uint64], ctypes.c_int),
     "gk_device_track": ([_P, ctypes.POINTER(_P), _U64P], ctypes.c_int),
+    "gk_minimizers": ([_P, _U8P, _U64P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U64P,
+                       _U32P], ctypes.c_int),
+    "gk_copy_minimizers": ([_P, _U64P, _U64P, _U8P, ctypes.c_uint64], ctypes.c_int),
+    "gk_device_minimizers": ([_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P), _U64P], ctypes.c_int),
+    "gk_select_minimizers": ([_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U64P], ctypes.c_int),
 }
 
 
@@ -731,6 +739,41 @@ class Engine:
                                           _ptr(first, ctypes.c_uint64) if want[1] else None,
                                           _ptr(count, ctypes.c_uint32) if want[2] else None))
         return longest, longest_pos, sum_len, lengths, first, count
+
+    # ---- minimizer sampling (gk_minimizers, gk_select_minimizers) -------------------------------
+    def minimizers(self, packed, k: int, w: int, flags: int = 0):
+        """(pos uint64[n] in the batch, key uint64[n], strand uint8[n], per_seq uint32[nseq]) of a
+        pack_sequences batch (gk_minimizers, then gk_copy_minimizers of the device view)."""
+        arr = np.ascontiguousarray(packed[0], dtype=np.uint8)
+        off = np.ascontiguousarray(packed[1], dtype=np.uint64)
+        if arr.ndim != 1 or off.ndim != 1 or off.size == 0:
+            raise ValueError("minimizers takes a 1-D uint8 array and its nseq + 1 offsets")
+        nseq = off.size - 1
+        n = ctypes.c_uint64(0)
+        per_seq = np.zeros(nseq, dtype=np.uint32)
+        self._check(self.lib.gk_minimizers(self.ctx, _ptr(arr, ctypes.c_uint8), _ptr(off, ctypes.c_uint64), nseq,
+                                           int(k), int(w), int(flags), ctypes.byref(n),
+                                           _ptr(per_seq, ctypes.c_uint32) if nseq else None))
+        pos = np.empty(n.value, dtype=np.uint64)
+        key = np.empty(n.value, dtype=np.uint64)
+        strand = np.empty(n.value, dtype=np.uint8)
+        self._check(self.lib.gk_copy_minimizers(self.ctx, _ptr(pos, ctypes.c_uint64), _ptr(key, ctypes.c_uint64),
+                                                _ptr(strand, ctypes.c_uint8), n.value))
+        return pos, key, strand, per_seq
+
+    def device_minimizers(self):
+        """(pos uint64*, key uint64*, strand uint8*, n) of the last minimizers (gk_device_minimizers)."""
+        p, q, s, n = _P(), _P(), _P(), ctypes.c_uint64()
+        self._check(self.lib.gk_device_minimizers(self.ctx, ctypes.byref(p), ctypes.byref(q), ctypes.byref(s),
+                                                  ctypes.byref(n)))
+        return p.value, q.value, s.value, n.value
+
+    def select_minimizers(self, k: int, w: int, flags: int = 0) -> int:
+        """The loaded sequence's minimizers become the start set (gk_select_minimizers); their number."""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.gk_select_minimizers(self.ctx, int(k), int(w), int(flags), ctypes.byref(n)))
+        self.n = n.value
+        return self.n
 
     # ---- the LCP array of the sorted order (gk_lcp) -------------------------------------------
     def lcp(self, max_len: int) -> np.ndarray:

@@ -44,6 +44,11 @@ ScreenResult = namedtuple("ScreenResult", ("n_windows", "n_present", "occurrence
 MatchResult = namedtuple("MatchResult", ("longest", "longest_pos", "sum_len", "lengths", "first", "count", "offsets"),
                          defaults=(None, None, None, None))
 MAX_MATCH_LEN = 4096  # the largest max_len of match_lengths when max_kmer_len is None
+# Kmers.minimizers' result: read j's minimizers are entries offsets[j] .. offsets[j + 1] of pos (offset
+# in the read), keys (the canonical 2-bit key) and strands (1: the key is the reverse complement's)
+MinimizerResult = namedtuple("MinimizerResult", ("offsets", "pos", "keys", "strands"))
+MAX_MINIMIZER_K = 32
+MAX_MINIMIZER_W = 256
 
 
 def maximal_from_lengths(lengths, offsets, min_len):
@@ -498,6 +503,7 @@ class Kmers:
         self._host_starts = None      # host view of the start indices (or a user-assigned array)
         self._host_valid = True       # _host_starts matches the device order
         self._device_stale = False    # a user-assigned array has not been uploaded yet
+        self._minimizer_spec = None   # (w, canonical, order) while the k-mer set is select_minimizers'
 
         if seq_coll is None:
             return
@@ -547,6 +553,7 @@ class Kmers:
         self._host_starts = None
         self._host_valid = False
         self._device_stale = False
+        self._minimizer_spec = None
 
     def _get_unfiltered_kmer_count(self) -> int:
         num_kmers = 0
@@ -590,6 +597,7 @@ class Kmers:
     @kmer_sba_start_indices.setter
     def kmer_sba_start_indices(self, value):
         self._canonical = False
+        self._minimizer_spec = None
         self._host_starts = value
         self._host_valid = True
         self._device_stale = True
@@ -964,6 +972,93 @@ class Kmers:
             return ScreenResult(n_windows, n_present, occurrences, wc, off)
         return ScreenResult(n_windows, n_present, occurrences)
 
+    # ---- minimizer sampling (no reference counterpart) -----------------------------------------
+    @staticmethod
+    def _minimizer_flags(what, k, w, canonical, order) -> int:
+        if order not in ("hash", "lex"):
+            raise ValueError(f"{what}: order must be 'hash' or 'lex' (order = {order!r})")
+        if not 1 <= k <= MAX_MINIMIZER_K:
+            raise ValueError(f"{what}: the k-mer length must be in 1..{MAX_MINIMIZER_K} (kmer_len = {k})")
+        if not 1 <= w <= MAX_MINIMIZER_W:
+            raise ValueError(f"{what}: w must be in 1..{MAX_MINIMIZER_W} (w = {w})")
+        return (_native.MINIMIZER_CANONICAL if canonical else 0) | (_native.MINIMIZER_LEX if order == "lex" else 0)
+
+    def minimizers(self, seqs, w: int, kmer_len: Union[int, None] = None, canonical: bool = False,
+                   order: str = "hash") -> MinimizerResult:
+        """The minimizers of every read of a batch, selected on the GPU (gk_minimizers).
+
+        ``seqs`` as for ``screen`` (_native.pack_sequences).  A window is ``w`` consecutive k-mers of
+        ``kmer_len`` bases (default: max_kmer_len, at most 32) made of A, C, G and T inside one read; its
+        minimizer is its leftmost k-mer of least order -- a 64-bit hash of the 2-bit key
+        (``order="hash"``) or the key itself (``"lex"``), with ``canonical`` of min(k-mer, reverse
+        complement).  Returns ``MinimizerResult``: ``offsets`` (int64, nseq + 1) into ``pos`` (uint32,
+        offset in the read, ascending per read), ``keys`` (uint64) and ``strands`` (uint8, 1 where the
+        key is the reverse complement's).  Needs no sorted index."""
+        if kmer_len is None:
+            kmer_len = self.max_kmer_len
+        if kmer_len is None:
+            raise ValueError("minimizers needs kmer_len (max_kmer_len is None)")
+        flags = self._minimizer_flags("minimizers", kmer_len, w, canonical, order)
+        arr, off = _native.pack_sequences(seqs)
+        # the batch needs no sequence: an object that has not uploaded its genome yet samples on a bare
+        # context of its own (no upload, no sort-hint pass), never stored as the object's engine
+        eng = self._engine
+        if eng is None:
+            eng = getattr(self, "_minimizer_engine", None)
+            if eng is None:
+                eng = self._minimizer_engine = _native.Engine()
+        pos, keys, strands, per_seq = eng.minimizers((arr, off), kmer_len, w, flags)
+        offsets = np.zeros(off.size, dtype=np.int64)
+        np.cumsum(per_seq, out=offsets[1:])
+        in_read = (pos - np.repeat(off[:-1], per_seq)).astype(np.uint32)
+        return MinimizerResult(offsets, in_read, keys, strands)
+
+    def select_minimizers(self, w: int, canonical: bool = False, order: str = "hash") -> int:
+        """Replace the k-mer set by the genome's minimizers, selected on the GPU (gk_select_minimizers);
+        returns their number.
+
+        Needs min_kmer_len == max_kmer_len <= 32.  The selection is ``minimizers``' with the genome as
+        one read ('$' and every letter but A, C, G, T end a run of windows), so a read that shares
+        w + k - 1 bases with the genome picks the same k-mer there.  The object is unsorted afterwards
+        and ``kmer_sba_start_indices`` reads the new set back on demand; ``sort``, ``find``,
+        ``get_kmer_locations``, ``count_in`` and ``lcp`` then work as on any assigned start subset.
+        (w, canonical, order) is remembered for ``find_minimizers`` until the start indices are assigned
+        or the object is initialised again."""
+        k = self.max_kmer_len
+        if k is None or k != self.min_kmer_len or k > MAX_MINIMIZER_K:
+            raise ValueError(f"select_minimizers needs min_kmer_len == max_kmer_len <= {MAX_MINIMIZER_K} "
+                             f"(min_kmer_len = {self.min_kmer_len}, max_kmer_len = {self.max_kmer_len})")
+        flags = self._minimizer_flags("select_minimizers", k, w, canonical, order)
+        self._check_forward()
+        n = self._get_engine().select_minimizers(k, w, flags)
+        self._device_stale = False  # (an assigned array not yet uploaded is replaced too)
+        self._host_starts = None
+        self._host_valid = False
+        self._is_sorted = False
+        self._canonical = False
+        self._minimizer_spec = (w, bool(canonical), order)
+        return n
+
+    def find_minimizers(self, seqs) -> tuple:
+        """``(MinimizerResult, first, count)``: the reads' minimizers under the remembered
+        select_minimizers spec, and ``find`` of each in this sorted sampled index.  The selected windows
+        are gathered from the packed reads on the host (the lookup does not stay on the device)."""
+        spec = getattr(self, "_minimizer_spec", None)
+        if spec is None:
+            raise ValueError("find_minimizers needs a k-mer set chosen by select_minimizers")
+        w, canonical, order = spec
+        if not self._is_sorted or self._canonical != canonical:
+            raise ValueError(f"find_minimizers needs sort(canonical={canonical}) after "
+                             f"select_minimizers(canonical={canonical})")
+        arr, off = _native.pack_sequences(seqs)
+        res = self.minimizers((arr, off), w, self.max_kmer_len, canonical, order)
+        in_batch = res.pos.astype(np.int64) + np.repeat(off[:-1].astype(np.int64), np.diff(res.offsets))
+        windows = arr[in_batch[:, None] + np.arange(self.max_kmer_len, dtype=np.int64)[None, :]]
+        if windows.shape[0] == 0:
+            return res, np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint32)
+        first, count = self.find(np.ascontiguousarray(windows))
+        return res, first, count
+
     # ---- matching statistics of reads (no reference counterpart) -------------------------------
     def _match_checks(self, what, max_len):
         """The preconditions of gk_match, checked on the host before any device call; returns the
@@ -1195,6 +1290,7 @@ class Kmers:
             self._host_starts = starts
             self._host_valid = True
             self._device_stale = starts is not None
+            self._minimizer_spec = None
         # a canonical sort saved by this build (the reference has no canonical order); any other
         # file restores a forward order, whatever this object held before
         self._canonical = bool(canonical)

@@ -494,6 +494,58 @@ int gk_match(gk_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint64_t
              uint32_t flags, uint32_t *longest, uint32_t *longest_pos, uint64_t *sum_len,
              uint32_t *match_len, uint64_t *match_first, uint32_t *match_count);
 
+/* Minimizer sampling of a batch of reads, or of the loaded sequence (no reference routine; the
+ * definition below is the contract).  seqs and offsets are gk_screen's batch; the offsets are checked by
+ * gk_screen's rules before any byte of seqs is read.  k is in 1..32, w in 1..256.
+ *   valid start  byte position p is a valid start if p + k <= the end of its sequence and its k bytes
+ *                are all 'A', 'C', 'G' or 'T'.  Any other byte -- '$', 'N', an IUPAC letter, a byte
+ *                outside the alphabet -- only ends a run: there is no alphabet error in these calls.
+ *   key(p)       the k bases as the 2-bit key in the low 2 k bits: A 0, C 1, G 2, T 3, the first base
+ *                most significant.  With GK_MINIMIZER_CANONICAL ckey = min(key, revcomp(key)) and
+ *                strand = 1 iff revcomp(key) < key (a k-mer equal to its reverse complement has strand
+ *                0); without the flag ckey = key and strand = 0.
+ *   ord(p)       with GK_MINIMIZER_LEX ord = ckey; otherwise ord = mix(ckey), mix(x) =
+ *                fmix64(x ^ 0x9E3779B97F4A7C15), fmix64(h): h ^= h >> 33; h *= 0xff51afd7ed558ccd;
+ *                h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53; h ^= h >> 33, all mod 2^64.  mix is a bijection,
+ *                so equal ords mean equal k-mers; the XOR keeps poly-A from hashing to 0.  ords compare
+ *                as unsigned 64-bit numbers.
+ *   window       w consecutive positions s .. s + w - 1 that are all valid starts of the same sequence
+ *                (at k = 1 consecutive valid starts can straddle two sequences: no window there).
+ *   minimizer    a window's minimizer is its leftmost position of least ord.
+ * The result is the set of positions that are the minimizer of at least one window, ascending, each
+ * with its ckey and strand; per sequence, the number of its positions in the set.  A run of fewer than
+ * w valid starts selects nothing; w = 1 selects every valid start.  The same set by a local rule: p is
+ * selected iff p is valid and L(p) + R(p) + 1 >= w, L(p) = the consecutive valid left neighbours in the
+ * same sequence with ord > ord(p), R(p) = the consecutive valid right neighbours with ord >= ord(p),
+ * both capped at w - 1.
+ * gk_minimizers needs a context, but no loaded sequence and no sort.  Each byte crosses to the device
+ * once, in chunks: a chunk owns a range of positions and carries w - 1 more bytes on its left and
+ * w - 1 + k - 1 on its right (fewer at the batch's ends); GKM_MINIMIZER_CHUNK (gk_set_option) lowers
+ * the positions a chunk owns.  The result stays on the device as a view -- pos uint64 (byte positions
+ * in the batch), key uint64, strand uint8, *n_out entries each -- until the next gk_minimizers or
+ * gk_destroy; the call touches no sort state, unique view, join result or LCP view.  per_seq (may be
+ * NULL, else nseq entries): the count of each sequence.  Integer results, the same on every run and for
+ * every chunk size.  nseq == 0 returns GK_OK with *n_out = 0 (an empty view).  A call refused with
+ * GK_E_ARG has touched nothing, an earlier view included; any other failure leaves no view.
+ * gk_copy_minimizers copies the view (each array may be NULL; n must equal the view's count, else
+ * GK_E_ARG); gk_device_minimizers gives the device arrays.  Both: GK_E_STATE without a view.
+ * gk_select_minimizers applies the same selection to the loaded sequence taken as one sequence (its '$'
+ * separators are invalid bytes, so no window crosses a contig end) and installs the selected positions,
+ * ascending, as the context's start set: the state gk_set_start_indices(ctx, those positions, n, k)
+ * would leave (min_kmer_len = k; the sort state, every view and a prefetched first pass dropped), the
+ * positions never visiting the host.  n_out may be NULL.  GK_E_STATE without a sequence; a call refused
+ * with GK_E_ARG or GK_E_STATE has touched nothing, a prefetched first pass included.
+ * All synchronise the stream.  GK_E_ARG: a null context, a null required pointer (offsets, n_out of
+ * gk_minimizers, seqs of a batch with bytes), k outside 1..32, w outside 1..256, unknown flag bits,
+ * offsets that break gk_screen's rules.  Each message names the values. */
+#define GK_MINIMIZER_CANONICAL 1u
+#define GK_MINIMIZER_LEX       2u
+int gk_minimizers(gk_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint64_t nseq,
+                  uint32_t k, uint32_t w, uint32_t flags, uint64_t *n_out, uint32_t *per_seq);
+int gk_copy_minimizers(gk_ctx *ctx, uint64_t *pos, uint64_t *key, uint8_t *strand, uint64_t n);
+int gk_device_minimizers(gk_ctx *ctx, void **pos, void **key, void **strand, uint64_t *n);
+int gk_select_minimizers(gk_ctx *ctx, uint32_t k, uint32_t w, uint32_t flags, uint64_t *n_out);
+
 /* ---- FASTA ingest (host; no context, no device) ------------------------------------------
  * gk_fasta_open maps `path` and scans it once with n_threads threads (<= 0: up to 16): the
  * number of records ('>' lines), the sequence bytes left after each line's strip(), and the bytes
